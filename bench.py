@@ -26,7 +26,8 @@ environments respawn before ONE observation pass) and `roofline.terminal_obs_onl
 `selfcheck` = four 64-environment slabs of this rank's batch replayed from reset through every step up to the end of
 the timed region -- by the CPU oracle, fed the Philox draws the kernel consumed -- and compared with the timed rollout's
 own outputs and state (non-zero exit status on a mismatch).  `cpu_baseline` = the CPU oracle timed on this host (rank 0,
-N = 1 only).
+N = 1 only).  `--dump-outputs DIR` writes what the last timed step returned to rank 0's caller as DIR/<name>.npy
+(`dump_outputs` in the line lists the files): the inputs are seeded, so two builds can be compared output for output.
 
 Other BASELINE.json workloads, not the headline:  --config 4  hard scenario, policy in the loop + gradient all-reduce;
                                                    --config 5  volley K=3 + HRL controller + resident LSTM state.
@@ -260,6 +261,43 @@ def measured_traffic(physics, n, form="single_pass"):
         return None, None
 
 
+DUMP_BYTES = 64 << 20                               # --dump-outputs: at most this much in all
+
+
+def step_outputs(ring, slot, env):
+    """What a caller of the timed path receives from one step, on the device: the ring slot the step wrote (obs, reward,
+    terminated, truncated) and the env's terminal observations and info planes (`step_torch`'s info).  Cloned, so that
+    later launches do not overwrite them.  The done list is left out: its order depends on the kernel's atomics."""
+    import torch
+    obs, rew, term, trunc = (x[slot].clone() for x in ring)
+    done = (term | trunc).bool()
+    keep = lambda x: torch.where(done.view(-1, *([1] * (x.dim() - 1))), x, torch.zeros_like(x))   # written for finished envs only
+    out = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc, "terminal_observation": keep(env.terminal_obs)}
+    for k, v in env.info.items():
+        v = v.T if v.dim() == 2 and v.shape[1] == obs.shape[0] else v      # [k, N] planes -> [N, k], one row per environment
+        out[k] = keep(v) if k in ("episode_return", "episode_length") else v.clone()
+    return out
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Writes `arrays` (name -> device tensor, one row per environment) as <path>/<name>.npy: float32 where the value is
+    float32 or narrower, float64 for int32.  If all rows would take more than `budget` bytes, a fixed sample of rows
+    (seed 0, sorted) is written instead, with its environment indices as env_index.npy.  Returns the list of files."""
+    host = {k: v.cpu().numpy() for k, v in arrays.items()}
+    host = {k: v.astype(np.float64 if v.dtype == np.int32 else np.float32) for k, v in host.items()}
+    n = len(next(iter(host.values())))
+    row_bytes = sum(v[:1].nbytes for v in host.values())
+    if n * row_bytes > budget:
+        m = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        host = {k: v[idx] for k, v in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(k + ".npy" for k in host)
+
+
 def tape_schedule(total, tape_len):
     """Successive (lo, hi) slices of the action tape covering `total` steps (the tape is re-read from its start)."""
     out, done = [], 0
@@ -304,9 +342,15 @@ def main():
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU work at all: the ranks rendezvous (gloo), run the barrier / max-over-ranks plumbing on a fake time "
                          "and rank 0 prints a line with value null -- checks the self-launch path on a machine without a GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's environments: obs, reward, terminated, truncated, "
+                         "terminal observations, info planes) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                         "(a fixed sample of environments beyond that); the same arguments give the same inputs on every run")
     args = ap.parse_args()
     if args.config == 3:
         args.physics = "v2dr"
+    if args.dump_outputs and (args.config in (4, 5) or args.rehearse_cpu):
+        raise SystemExit("--dump-outputs: only the flagship workload (--config 2 / 3) dumps its outputs")
     forms = [f for f in args.forms.split(",") if f]
     for f in forms:
         if f not in FORM_BYTES_DELTA:
@@ -480,6 +524,7 @@ def main():
     if check is not None:             # what the slabs and the oracle will be compared with: taken here, right behind the timed region
         big_last = tuple(x[last_slot].clone() for x in ring)
         big_state = env.get_state()
+    last_outputs = step_outputs(ring, last_slot, env) if args.dump_outputs and rank == 0 else None
 
     # ---------------------------------------------------------------- event-clocked windows, one set per form
     measured = {form: windows(form) for form in forms}
@@ -535,6 +580,12 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(rc)
 
+    dumped = None
+    if last_outputs is not None:
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last_outputs),
+                  "step": "the last of the K timed steps", "envs": n}
+        last_outputs = None
+
     if rank == 0:
         traffic, traffic_src = measured_traffic(args.physics, n, forms[0])
         roof = {"bound": "hbm", "achieved": head["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": head["frac"],
@@ -577,6 +628,7 @@ def main():
             "cpu_baseline": cpu,
             "fused_rollout": fused,
             "extra_points": extra,
+            "dump_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if extra is None:

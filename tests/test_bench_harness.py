@@ -155,3 +155,61 @@ def test_bench_two_ranks_on_one_device_over_gloo():
                "--preroll", "200", "--no-extra-points", "--no-cpu-baseline", "--fused", "0", "--forms", "contract")
     assert d["n_gpus"] == 2 and d["ranks"]["dist_world_size"] == 2 and d["ranks"]["backend"] == "gloo" and len(d["ranks"]["per_rank_ms"]) == 2
     assert all(_finite(x) and x > 0 for x in d["ranks"]["per_rank_ms"]) and _finite(d["value"]) and d["selfcheck"]["ok"]
+
+
+def test_dump_outputs_writes_one_row_per_env_and_samples_beyond_the_budget(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files of one row per environment; rows of the terminal observation and of
+    the episode totals are kept for the environments that finished in the step only; beyond the byte budget a fixed sample
+    of environments (with its indices) is written, the same one on every call."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1000
+    g = torch.Generator().manual_seed(0)
+    ring = (torch.rand((2, n, 26), generator=g), torch.rand((2, n), generator=g),
+            (torch.rand((2, n), generator=g) < 0.1).to(torch.uint8), (torch.rand((2, n), generator=g) < 0.1).to(torch.uint8))
+    packed = torch.rand((3, n, 4), generator=g)
+    env = types.SimpleNamespace(terminal_obs=torch.rand((n, 26), generator=g),
+                                info={"episode_return": torch.rand(n, generator=g), "episode_length": torch.arange(n, dtype=torch.int32),
+                                      "fuel": packed[0, :, 2], "interceptor_pos": packed[1, :, 0:3].T,
+                                      "steps": packed.view(torch.int32)[1, :, 3], "flags": packed.view(torch.uint8)[2, :, 12]})
+    out = bench.step_outputs(ring, 1, env)
+    ring[0].zero_()
+    env.terminal_obs.zero_()                                        # later launches overwrite the buffers: the snapshot stays
+    files = bench.dump_outputs(str(tmp_path / "all"), out)
+    assert "env_index.npy" not in files and len(files) == len(out)
+    a = {f[:-4]: np.load(tmp_path / "all" / f) for f in files}
+    done = (ring[2][1] | ring[3][1]).bool().numpy()
+    assert a["obs"].dtype == np.float32 and a["obs"].shape == (n, 26) and np.any(a["obs"] != 0) and a["interceptor_pos"].shape == (n, 3)
+    assert a["episode_length"].dtype == np.float64 and a["flags"].dtype == np.float32 and a["terminated"].dtype == np.float32
+    assert np.all(a["terminal_observation"][~done] == 0) and np.all(a["episode_length"][~done] == 0)
+    assert np.array_equal(a["episode_length"][done], np.flatnonzero(done).astype(np.float64))
+    budget = 300 * sum(v[:1].nbytes for v in a.values())
+    f1 = bench.dump_outputs(str(tmp_path / "s1"), out, budget=budget)
+    f2 = bench.dump_outputs(str(tmp_path / "s2"), out, budget=budget)
+    assert f1 == f2 and "env_index.npy" in f1
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in f1) <= budget + 128 * len(f1)     # (+ the .npy headers)
+    idx = np.load(tmp_path / "s1" / "env_index.npy").astype(np.int64)
+    assert len(idx) < n and np.all(np.diff(idx) > 0)
+    for f in f1:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+    assert np.array_equal(np.load(tmp_path / "s1" / "obs.npy"), a["obs"][idx])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """Two runs with the same arguments time exactly --steps launches and dump identical outputs of the last one."""
+    import numpy as np
+    args = ("--envs-per-gpu", "4096", "--steps", "20", "--warmup", "5", "--desync", "256", "--preroll", "200", "--no-extra-points",
+            "--no-cpu-baseline", "--fused", "0", "--forms", "contract")
+    d1 = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    d2 = _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert d1["steps"] == 20 and d1["roofline"]["timed_region"]["launches"] == 20 and _finite(d1["ms_per_step"]) and d1["selfcheck"]["ok"]
+    files = d1["dump_outputs"]["files"]
+    assert files == d2["dump_outputs"]["files"] and {"obs.npy", "reward.npy", "terminated.npy", "truncated.npy"} <= set(files)
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and len(x) == 4096 and np.array_equal(x, y, equal_nan=True), f
+    assert np.all(np.isfinite(np.load(tmp_path / "a" / "obs.npy")))
