@@ -8,9 +8,13 @@ The faces, imported on first use (nothing here imports torch or loads the librar
     InterceptEnvironment single_env   ONE environment with the reference's class name and `gym.Env` semantics
     VecFrameStack, VecNormalize  wrappers   the two SB3 wrappers of the reference's trainers, on the device
     HRLController        hrl          the hierarchical wrapper's per-environment logic, on the device
+    evaluate_classical_policy, evaluate_policy, aggregate_metrics, PurePursuit, ProportionalNavigation, AugmentedPN
+                         evaluation   the paper benchmark's guidance laws and per-episode metrics, on the device
 """
 _EXPORTS = {"HlynrVecEnv": "vec_env", "HlynrGymVectorEnv": "gym_vector", "ShardedHlynrVecEnv": "sharded",
-            "InterceptEnvironment": "single_env", "VecFrameStack": "wrappers", "VecNormalize": "wrappers", "HRLController": "hrl"}
+            "InterceptEnvironment": "single_env", "VecFrameStack": "wrappers", "VecNormalize": "wrappers", "HRLController": "hrl",
+            "evaluate_classical_policy": "evaluation", "evaluate_policy": "evaluation", "aggregate_metrics": "evaluation",
+            "PurePursuit": "evaluation", "ProportionalNavigation": "evaluation", "AugmentedPN": "evaluation"}
 __all__ = sorted(_EXPORTS)
 
 

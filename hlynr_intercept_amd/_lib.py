@@ -13,7 +13,7 @@ from . import build as _build
 f32, i32, u32, i64, u64, f64, u8p = C.c_float, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_double, C.c_void_p
 
 OBS_DIM, ACT_DIM, STEP_SLOTS, RESET_SLOTS, RING_CAP, MAX_STEPS, MAX_VOLLEY = 26, 6, 32, 48, 11, 8191, 4
-ABI_VERSION = 4      # include/hlx.h HLX_ABI_VERSION: the revision these ctypes mirrors were written for
+ABI_VERSION = 5      # include/hlx.h HLX_ABI_VERSION: the revision these ctypes mirrors were written for
 
 # hlx_flags
 F_ATMOSPHERE, F_MACH_DRAG, F_ENH_WIND, F_THRUST_LAG, F_DOMAIN_RAND, F_VALIDATION, F_EVASION, F_PRECISION = (
@@ -159,6 +159,25 @@ SYMBOLS = {
     "hlx_hrl_bind_order": (C.c_int, [_P, _P, _P]),
 }
 
+
+class HlxEvalConfig(C.Structure):   # include/hlx_eval.h hlx_eval_config
+    _fields_ = [("n_envs", i32), ("device", i32), ("law", i32), ("use_true_state", i32), ("episodes_per_env", i32),
+                ("pad0", i32), ("N", f64), ("K_acc", f64), ("kill_radius", f64)]
+
+
+LAW_NONE, LAW_PURSUIT, LAW_PN, LAW_APN = 0, 1, 2, 3      # include/hlx_eval.h HLX_LAW_*
+
+# every symbol include/hlx_eval.h declares (kept apart from SYMBOLS, which mirrors hlx.h, hlx_obs.h and hlx_hrl.h)
+EVAL_SYMBOLS = {
+    "hlx_eval_create": (C.c_int, [C.POINTER(HlxEvalConfig), C.POINTER(_P)]),
+    "hlx_eval_destroy": (C.c_int, [_P]),
+    "hlx_eval_begin": (C.c_int, [_P, _P, _P, _P]),
+    "hlx_eval_observe": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(HlxInfoSoa), _P, _P]),
+    "hlx_eval_run": (C.c_int, [_P, _P, i32, i32, _P, C.POINTER(i64), _P]),
+    "hlx_eval_done_count": (C.c_int, [_P, C.POINTER(i32), _P]),
+    "hlx_eval_records": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _load_error = None
 
@@ -228,7 +247,7 @@ def _load(build_if_missing: bool):
     if abi() != ABI_VERSION:
         raise RuntimeError(f"{path} implements ABI revision {abi()} of include/hlx.h, this binding revision {ABI_VERSION}: rebuild it "
                            "(python -m hlynr_intercept_amd.build)")
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(EVAL_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError = symbol missing = broken build
         fn.restype, fn.argtypes = res, args
     for what, c_size, py_size in (("hlx_config", lib.hlx_sizeof_config(), C.sizeof(HlxConfig)),

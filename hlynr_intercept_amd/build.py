@@ -10,7 +10,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.environ.get("HLX_LIBRARY") or os.path.join(_HERE, "libhlx.so")   # HLX_LIBRARY: diagnostic builds
 SOURCES = ["hlx_kernels.hip"]
 DEPS = ["hlx_kernels.hip", "hlx_inst_gen.h", "hlx_host.inc", "hlx_obs.inc", "hlx_device.h", "hlx_kargs.h", "hlx_kcfg.h", "hlx_bake_gen.cpp", os.path.join("..", "..", "include", "hlx.h"),
-        os.path.join("..", "..", "include", "hlx_obs.h"), "hlx_hrl.inc", os.path.join("..", "..", "include", "hlx_hrl.h")]
+        os.path.join("..", "..", "include", "hlx_obs.h"), "hlx_hrl.inc", os.path.join("..", "..", "include", "hlx_hrl.h"),
+        "hlx_eval.inc", os.path.join("..", "..", "include", "hlx_eval.h")]
 
 
 SAFE_FLAGS = ["-DHLX_HOT_FROM_MEMORY=1"]

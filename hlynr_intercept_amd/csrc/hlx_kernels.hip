@@ -2136,4 +2136,6 @@ void hlx_launch(dim3 grid, hipStream_t s, const StepArgs& a) {
 #include "hlx_obs.inc"
 // on-device HRL controller logic (include/hlx_hrl.h)
 #include "hlx_hrl.inc"
+// closed-loop evaluation of the classical guidance laws (include/hlx_eval.h)
+#include "hlx_eval.inc"
 #endif

@@ -368,7 +368,7 @@ int32_t hlx_sizeof_env_state(void);
 int32_t hlx_sizeof_info_soa(void);
 /* ABI revision of this header (HLX_ABI_VERSION): bumped whenever a struct grows or an entry point changes meaning, so that a
  * binding can refuse a library built from another revision even where it cannot rebuild it (hlynr_intercept_amd/_lib.py). */
-#define HLX_ABI_VERSION 4
+#define HLX_ABI_VERSION 5
 int32_t hlx_abi_version(void);
 /* 1 if this library is the SAFE build (-DHLX_HOT_FROM_MEMORY=1: the step kernel reads its constants from the parameter block in
  * memory instead of across lanes out of two vector registers -- what the build falls back to when the disassembly lint refuses the
