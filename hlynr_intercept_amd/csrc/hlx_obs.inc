@@ -193,8 +193,9 @@ __global__ __launch_bounds__(256) void hlx_obs_moments_pair_kernel(ObsK k, const
             __syncthreads();
             lds[t][0] = s0[back]; lds[t][1] = q0[back]; lds[t][2] = s1[back]; lds[t][3] = q1[back];
             __syncthreads();
-            if (t < 4 * H) {
-                const int mm = t >> 2, w = t & 3;
+            // 4 H outputs per position; for D > 128 the block (R H threads, R <= 3) has fewer threads than that
+            for (int q = t; q < 4 * H; q += blockDim.x) {
+                const int mm = q >> 2, w = q & 3;
                 double a = 0.;
                 for (int rr = 0; rr < R; ++rr) a += lds[rr * H + mm][w];
                 const int col = (S - 1 - back) * k.D + 2 * mm + (w >> 1);   // w: 0 sum.x, 1 sq.x, 2 sum.y, 3 sq.y
@@ -289,8 +290,8 @@ __global__ __launch_bounds__(256) void hlx_obs_moments_inc_kernel(ObsK k, const 
         __syncthreads();
         lds[t][0] = s0[back]; lds[t][1] = q0[back]; lds[t][2] = s1[back]; lds[t][3] = q1[back];
         __syncthreads();
-        if (t < 4 * H) {
-            const int mm = t >> 2, w = t & 3;
+        for (int q = t; q < 4 * H; q += blockDim.x) {     // (as in hlx_obs_moments_pair_kernel: D > 128 loops)
+            const int mm = q >> 2, w = q & 3;
             double a = 0.;
             for (int rr = 0; rr < R; ++rr) a += lds[rr * H + mm][w];
             const int col = (S - 1 - back) * k.D + 2 * mm + (w >> 1);

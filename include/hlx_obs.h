@@ -28,6 +28,14 @@
  * batch moments, merges the running statistics and emits the stacked, normalised [N][n_stack*D] float32 batch the
  * policy consumes.  All pointers are DEVICE pointers unless stated; nothing synchronises; every function returns
  * an hlx_status (hlx.h) and sets hlx_last_error().
+ *
+ * Conditioning: the batch variance is one-pass, sum(x^2)/n - mean^2 in float64, where SB3 takes a two-pass np.var.
+ * Measured against a float64 two-pass reference (tests/test_obs_pipeline_gpu.py), its relative error is ~1e-10 at
+ * |mean|/std = 1e3 and 2e-9..5e-9 at 1e4: the running variance keeps 1e-9 relative agreement up to |mean|/std = 1e3
+ * per column and batch.  Column 12 of the intercept observation reaches 1.8e4 (medium/base) to 1.8e5 (medium/v2dr) in
+ * single batches; its running variance, which also holds the spread between batches, has stayed within 1e-9 in every
+ * wrapper test so far.  The incremental forms (a push's column sums = the last push's sums minus the rows that leave)
+ * leave a residue of ~1e-16 x the leaving sum of squares where a column empties.
  */
 #ifndef HLX_OBS_H
 #define HLX_OBS_H

@@ -98,13 +98,15 @@ class Normalize:
         return self.normalize_obs(stacked)
 
     def step(self, stacked, reward, dones, terminal_stacked):
+        """reward=None: no return update on this step (include/hlx_obs.h hlx_obs_push with reward NULL); the returns of
+        finished environments are still zeroed, and the normalised reward is None."""
         if self.training and self.norm_obs:
             self.obs_rms.update(stacked, self.batch_f32)
         obs_n = self.normalize_obs(stacked)
-        if self.training:                                          # _update_reward, also when norm_reward is off
+        if self.training and reward is not None:                   # _update_reward, also when norm_reward is off
             self.returns = self.returns * self.gamma + reward
             self.ret_rms.update(self.returns, False)
-        reward_n = self.normalize_reward(reward)
+        reward_n = None if reward is None else self.normalize_reward(reward)
         term_n = self.normalize_obs(terminal_stacked)              # rows of finished envs are the meaningful ones
         self.returns[dones] = 0
         return obs_n, reward_n, term_n

@@ -62,3 +62,25 @@ def test_normalize_clips_and_zeroes_returns_on_done():
     frozen = Normalize(n, F, training=False)
     frozen.step(np.ones((n, F), np.float32), np.ones(n, np.float32), np.zeros(n, bool), np.zeros((n, F), np.float32))
     assert frozen.obs_rms.count == 1e-4 and np.all(frozen.returns == 0)   # evaluation mode touches nothing
+
+
+def test_normalize_step_without_reward_skips_the_return_update_only():
+    n, F = 32, 6
+    rng = np.random.default_rng(3)
+    a, b = Normalize(n, F, gamma=0.9), Normalize(n, F, gamma=0.9)
+    obs = rng.normal(size=(n, F)).astype(np.float32)
+    a.reset(obs)
+    b.reset(obs)
+    rew = rng.normal(size=n).astype(np.float32)
+    nodone = np.zeros(n, bool)
+    a.step(obs, rew, nodone, np.zeros((n, F), np.float32))
+    b.step(obs, rew, nodone, np.zeros((n, F), np.float32))
+    dones = rng.random(n) < 0.5
+    o_a, r_a, _ = a.step(obs, None, dones, np.zeros((n, F), np.float32))
+    o_b, _, _ = b.step(obs, rew, dones, np.zeros((n, F), np.float32))
+    assert r_a is None
+    np.testing.assert_array_equal(o_a, o_b)                            # observation statistics move the same way
+    assert a.obs_rms.count == b.obs_rms.count
+    assert a.ret_rms.count == 1e-4 + n and b.ret_rms.count == 1e-4 + 2 * n   # ... the return statistics do not
+    assert np.all(a.returns[dones] == 0) and np.all(a.returns[~dones] != 0)   # finished environments are still zeroed
+    np.testing.assert_array_equal(a.returns[~dones], (rew.astype(np.float64))[~dones])   # the others keep last step's return

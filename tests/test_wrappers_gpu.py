@@ -150,15 +150,19 @@ def test_sb3_numpy_contract_of_the_wrapped_env():
 @pytest.mark.parametrize("n,n_stack", [(4099, 4), (300, 2), (70, 8), (9000, 4)])
 def test_incremental_moments_equal_the_full_reduction(n, n_stack):
     """Step pushes that follow a training push reduce only the newest frame and subtract the frames of the environments
-    that were reset (hlx_obs_moments_inc_kernel); HLX_OBS_FULL_MOMENTS=1 forces the full reduction over all n_stack frames.
-    Same batches, both ways: the running statistics agree to float64 rounding, including across eval-mode gaps."""
+    that were reset.  By default the step kernel itself writes the newest frame's partial sums and
+    hlx_obs_finalize_fused_kernel subtracts the leaving frames; HLX_OBS_NO_FUSE=1 takes the same incremental sums from
+    hlx_obs_moments_inc_kernel instead; HLX_OBS_FULL_MOMENTS=1 forces the full reduction over all n_stack frames.
+    Same batches, all three ways: the running statistics agree to float64 rounding, including across eval-mode gaps."""
     import torch
     from hlynr_intercept_amd.wrappers import VecFrameStack, VecNormalize
     T = 90
     stats = {}
-    for full in (False, True):
-        if full:
-            os.environ["HLX_OBS_FULL_MOMENTS"] = "1"
+    for form in ("fused", "full", "no_fuse"):
+        full = form == "full"
+        env_var = {"fused": None, "full": "HLX_OBS_FULL_MOMENTS", "no_fuse": "HLX_OBS_NO_FUSE"}[form]
+        if env_var:
+            os.environ[env_var] = "1"
         try:
             w = VecNormalize(VecFrameStack(_make(n, seed=21, max_steps=17), n_stack), norm_reward=True)
             g = torch.Generator(device=w.device).manual_seed(8)
@@ -173,13 +177,19 @@ def test_incremental_moments_equal_the_full_reduction(n, n_stack):
                 w.step_torch(acts[t])
                 if t % 10 == 9:
                     snaps.append((w.obs_rms.mean.copy(), w.obs_rms.var.copy(), w.obs_rms.count, w.ret_rms.var))
-            stats[full] = snaps
+            stats[full if form != "no_fuse" else form] = snaps
             w.close()
         finally:
-            os.environ.pop("HLX_OBS_FULL_MOMENTS", None)
+            if env_var:
+                os.environ.pop(env_var, None)
     for (m0, v0, c0, r0), (m1, v1, c1, r1) in zip(stats[False], stats[True]):
         # (the return sums: identical order in the incremental and the full kernel; one more order since round 3, when the step
         # kernel forms them per 64-environment block -- float64 rounding apart)
+        assert c0 == c1 and abs(r0 - r1) <= 1e-13 * max(1.0, abs(r1))
+        assert np.max(np.abs(m0 - m1)) <= 1e-12 * max(1.0, np.max(np.abs(m1)))
+        assert np.max(np.abs(v0 - v1)) <= 1e-11 * max(1.0, np.max(np.abs(v1)))
+    assert len(stats["no_fuse"]) == len(stats[True])
+    for (m0, v0, c0, r0), (m1, v1, c1, r1) in zip(stats["no_fuse"], stats[True]):
         assert c0 == c1 and abs(r0 - r1) <= 1e-13 * max(1.0, abs(r1))
         assert np.max(np.abs(m0 - m1)) <= 1e-12 * max(1.0, np.max(np.abs(m1)))
         assert np.max(np.abs(v0 - v1)) <= 1e-11 * max(1.0, np.max(np.abs(v1)))
