@@ -933,6 +933,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         float4 coop[COOP_MAX];                 // (deliberately uninitialised, like `pf`: written and read under `coop_mask` only)
         const bool coop_whole = n - (int)blockIdx.x * 64 >= 64;      // a whole block: every lane of the wave is at work
         unsigned long long coop_mask = 0ull;   // the finished lanes of this wave whose prepared episode the wave copies
+        unsigned long long coop_load = 0ull;   // ... as loaded: coop[k] holds the entry of its k-th set bit (the beam check below may clear bits of coop_mask)
         unsigned long long coop_over = 0ull;   // ... and the ones beyond COOP_MAX with a good entry: computed in place, counted apart from misses
         float2 coop_beam = make_float2(2.f, -2.f);   // a finished lane's OWN copy of the beam test its entry was computed with (cosine, threshold)
         float4 pf[POOL_GROUPS];
@@ -954,6 +955,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     }
                 }
                 coop_over = m;
+                coop_load = coop_mask;
                 hit_pf = ((coop_mask >> lane) & 1ull) != 0ull;
                 // (the finished lane fetches the two floats that decide whether its entry is still valid for itself: a cross-lane
                 // read of the quad above would be a v_readlane of a register the allocator may have parked in an accumulation
@@ -1155,7 +1157,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                             // cosine of the off-boresight angle against the threshold.  The entry carries that cosine and the threshold it
                             // was compared with; it is the first observation under TODAY's threshold too iff both comparisons fall on
                             // the same side, by more than the margin inside which the decision replays the reference's arithmetic.
-                            // (A new episode looks straight at its missile -- cosine 1 -- so a beam ramp invalidates next to nothing; rounds
+                            // (A new episode looks straight at its missile -- cosine 1 -- so a ramp through the shipped widths invalidates
+                            // next to nothing, a beam below ~0.5 degrees every in-range entry; rounds
                             // before this one renewed ALL entries, a 12-45 us launch, ahead of every step of the ramp.)
                             const float cbe = acc_read(pf[PG_ROW + (HLX_OBS_DIM + 3) / 4 - 1].z), cte = acc_read(pf[PG_ROW + (HLX_OBS_DIM + 3) / 4 - 1].w);
                             const float ctn = cur_cos_half_beam;
@@ -1956,12 +1959,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             const bool on_word = g == PG_ON && HOT(c.o_delay) > 0;
             const bool gr_word = g >= PG_GR && g < PG_ROW && HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0;
             const bool row_word = g >= PG_ROW && g < POOL_GROUPS;
-            unsigned long long mm = coop_mask;
+            // (slot k belongs to the k-th set bit of the mask it was LOADED for; a lane whose entry failed the beam check has left
+            // coop_mask, its slot is skipped -- walking the reduced mask instead would hand a later lane the dropped lane's entry)
+            unsigned long long mm = coop_load;
 #pragma unroll
             for (int k = 0; k < COOP_MAX; ++k) {
                 if (mm != 0ull) {
                     const uint32_t d = (uint32_t)__builtin_ctzll(mm);
                     mm &= mm - 1ull;
+                    if (((coop_mask >> d) & 1ull) == 0ull) continue;      // (wave-uniform)
                     const uint32_t e = (uint32_t)blockIdx.x * 64u + d;      // the finished environment
                     uint32_t off = 0u;
                     if (st_word) off = (uint32_t)blockIdx.x * (uint32_t)(N_GROUPS * 1024) + (uint32_t)g * 1024u + d * 16u;

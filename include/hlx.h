@@ -332,7 +332,8 @@ int hlx_get_episode_pool_crowded(hlx_env *env, int64_t *crowded);
  * step, train_flat_ppo.py:171-177).  A first observation reads three curriculum scalars.  The radar BEAM WIDTH -- the one the
  * shipped curriculum ramps (config.yaml:85-92) -- costs nothing: every prepared episode remembers the beam test it was computed
  * with and is used only if today's threshold decides it the same way (a new episode looks straight at its missile, so a ramp
- * invalidates next to nothing).  A sensor RELIABILITY that moves makes every prepared episode stale: while one is moving the pool
+ * through the shipped widths invalidates next to nothing; below about 0.5 degrees every in-range entry falls inside the margin
+ * and is computed in place -- slower, same bits).  A sensor RELIABILITY that moves makes every prepared episode stale: while one is moving the pool
  * is suspended (next episodes are computed in place, as without a pool) and is filled again once the scalars have stood still
  * for 16 step launches.  out[4] = {auto-resets computed inside step launches with the pool in use, full fills, partial fills,
  * step launches issued while the pool was suspended} (synchronises; diagnostics). */

@@ -783,7 +783,8 @@ def test_next_episode_pool_under_a_curriculum_that_moves_every_step(ramp):
     """The reference's trainers call set_training_step_count after EVERY step (train_flat_ppo.py:171-177) and the shipped
     radar curriculum ramps the beam width over 3 M steps (config.yaml:85-92).  Round 3 renewed every prepared episode ahead
     of every step of such a ramp (advisor finding).  Now: a beam ramp costs no fill at all -- entries carry the beam test they
-    were computed with and are validated against today's threshold, and a new episode looks straight at its missile -- and a
+    were computed with and are validated against today's threshold, and a new episode looks straight at its missile, so at the
+    shipped widths next to no entry is dropped (below ~0.5 degrees every in-range one is: tests/test_episode_pool_gpu.py) -- and a
     reliability ramp suspends the pool until the scalars have stood still for 16 steps.  Either way: same bits as no pool."""
     import torch
     n, T = 1300, 150
