@@ -88,29 +88,12 @@ DEV float div_rn(float a, float b) {
     return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y, q1);
 }
 
-#ifndef HLX_SHORT_SQRT
-#define HLX_SHORT_SQRT 1
-#endif
-#if HLX_SHORT_SQRT
-#define HLX_SQRTF(x) sqrt_rn(x)
-#else
-#define HLX_SQRTF(x) __builtin_sqrtf(x)
-#endif
-
-#ifndef HLX_SHORT_DIV
-#define HLX_SHORT_DIV 1
-#endif
-#if HLX_SHORT_DIV
-#define HLX_DIVF(a, b) div_rn((a), (b))
-#else
-#define HLX_DIVF(a, b) ((a) / (b))
-#endif
 // vector / norm-like scalar: every caller divides by a guarded norm (> 1e-6) or an O(1) physical scale
-DEV V3 operator/(V3 a, float s) { return V3{HLX_DIVF(a.x, s), HLX_DIVF(a.y, s), HLX_DIVF(a.z, s)}; }
+DEV V3 operator/(V3 a, float s) { return V3{div_rn(a.x, s), div_rn(a.y, s), div_rn(a.z, s)}; }
 
 // numpy float32 dot / norm (OpenBLAS sdot): float32 products, float64 accumulation, one rounding
 DEV float sdot3(V3 a, V3 b) { return (float)(((double)(a.x * b.x) + (double)(a.y * b.y)) + (double)(a.z * b.z)); }
-DEV float snorm3(V3 a) { return HLX_SQRTF(sdot3(a, a)); }
+DEV float snorm3(V3 a) { return sqrt_rn(sdot3(a, a)); }
 DEV V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 DEV float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 // x / c with c a constant whose float64 reciprocal is `inv`
@@ -173,10 +156,10 @@ DEV float fast_asin(float x) {
     p = __builtin_fmaf(ax, p, 0.0889789874f);
     p = __builtin_fmaf(ax, p, -0.2145988016f);
     p = __builtin_fmaf(ax, p, 1.5707963050f);
-    return copysignf(1.5707963267948966f - HLX_SQRTF(1.0f - ax) * p, x);
+    return copysignf(1.5707963267948966f - sqrt_rn(1.0f - ax) * p, x);
 }
 DEV float fdot(V3 a, V3 b) { return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)); }
-DEV float fnorm(V3 a) { return HLX_SQRTF(fdot(a, a)); }
+DEV float fnorm(V3 a) { return sqrt_rn(fdot(a, a)); }
 // for pure outputs (observation entries, data-link / fusion scores): the raw 1-ulp v_sqrt_f32
 DEV float fnorm_out(V3 a) { return __builtin_amdgcn_sqrtf(fdot(a, a)); }
 
@@ -325,7 +308,7 @@ DEV void atmosphere(float alt, float T0, float& rho, float& sos, const PowTab* t
     constexpr float GAMMA_R = (float)(1.4 * 287.05);
     // troposphere for every lane; the upper layers (not reachable in the shipped scenarios) override it out of line
     float T = T0 - L * alt;                       // :70-71
-    float P = 101325.0f * pow_ref(HLX_DIVF(T, T0), EXPO, tab);   // :95-100
+    float P = 101325.0f * pow_ref(div_rn(T, T0), EXPO, tab);   // :95-100
     if (__builtin_expect(alt > 11000.0f, 0)) {
         if (alt <= 20000.0f) {                    // :72-74,102-108
             T = 216.65f;
@@ -337,8 +320,8 @@ DEV void atmosphere(float alt, float T0, float& rho, float& sos, const PowTab* t
             P = Pb * exp_np(-ex / 6000.0f);
         }
     }
-    rho = HLX_DIVF(P, R * T);                     // :166
-    sos = HLX_SQRTF(GAMMA_R * T);                     // :167-169
+    rho = div_rn(P, R * T);                     // :166
+    sos = sqrt_rn(GAMMA_R * T);                     // :167-169
 }
 
 struct DragParams {
@@ -348,16 +331,16 @@ struct DragParams {
 // physics_models.py:236-264  drag force vector (float32 velocity); `area` = reference_area
 DEV V3 mach_drag_force(V3 v, float rho, float sos, float area, const DragParams& p) {
     float vm = snorm3(v);
-    float mach = HLX_DIVF(vm, sos);                                          // :233-234
+    float mach = div_rn(vm, sos);                                          // :233-234
     float cd = p.base_cd;                                                   // :207-209 subsonic; the other regimes out of line
     if (__builtin_expect(!(mach < p.subsonic), 0)) {
         if (mach < p.supersonic) {
-            float frac = HLX_DIVF(mach - p.subsonic, p.mach_span);          // :213-214
+            float frac = div_rn(mach - p.subsonic, p.mach_span);          // :213-214
             cd = p.base_cd * (1.0f + p.peak_m1 * frac);                     // :215-216 ((peak - 1.0) is a Python-float expression)
         } else cd = p.cd_super;                                             // :220 (python-float product)
     }
     float a = (((0.5f * rho) * (vm * vm)) * cd) * area;                     // :258
-    V3 f = V3{HLX_DIVF(-v.x, vm) * a, HLX_DIVF(-v.y, vm) * a, HLX_DIVF(-v.z, vm) * a};   // :262-264
+    V3 f = V3{div_rn(-v.x, vm) * a, div_rn(-v.y, vm) * a, div_rn(-v.z, vm) * a};   // :262-264
     if (__builtin_expect(vm < 1e-6f, 0)) f = v3(0.f, 0.f, 0.f);             // :238-239 (an override, not an early return: out of line)
     return f;
 }

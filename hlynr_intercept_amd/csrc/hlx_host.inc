@@ -317,8 +317,9 @@ int pool_fill(hlx_env* e, bool all, hipStream_t s) {
     return HLX_OK;
 }
 // Ahead of a step launch: a stale pool is filled entirely; the entries used since the last fill are renewed once `pool_interval`
-// steps have gone by -- ahead of launches that can use them only (`consumes`: the two-pass forms of the step; the single-pass
-// form and the fused rollout compute their respawns in place, and a rollout made of them alone never pays for a fill).
+// steps have gone by -- ahead of launches that can use them only (`consumes`: the step launches without noise buffers, every one of
+// them two-pass under the lone-wave schedule; the fused rollout computes its respawns in place, and a rollout made of it alone never
+// pays for a fill).
 int pool_before_step(hlx_env* e, hipStream_t s, bool consumes = false) {
     if (e->ep_zero_pending && (!e->pool_on || e->load_sched != 2)) {
         HIP_TRY(hipMemsetAsync(e->ep_cur, 0, sizeof(uint32_t) * (((size_t)e->n + 63) / 64) * 64, s));
@@ -708,14 +709,9 @@ static int step_impl(hlx_env* e, const float* actions, float* obs, float* reward
     }
     int rc = sync_params(e, want, s);
     if (rc) return rc;
-    {
-        const bool any_info = info_any(want.info);
-#ifndef HLX_LONE_NEVER_SINGLE
-#define HLX_LONE_NEVER_SINGLE 1     // (hlx_kernels.hip: under the lone-wave schedule every form of the step uses pool entries)
-#endif
-        rc = pool_before_step(e, s, (HLX_LONE_NEVER_SINGLE || terminal_obs != nullptr || any_info) && !e->step_noise && !e->reset_noise);
-        if (rc) return rc;
-    }
+    // (hlx_kernels.hip: under the lone-wave schedule every form of the step uses pool entries)
+    rc = pool_before_step(e, s, !e->step_noise && !e->reset_noise);
+    if (rc) return rc;
     e->t += 1;  // this launch's clock value
     KIo io{actions, obs, reward, terminated, truncated};
     if (e->prof && bracket) { rc = prof_event(e, s); if (rc) return rc; }

@@ -48,13 +48,6 @@ namespace {
 // rare branches: laid out of line so that the hot path is one contiguous instruction stream (the step is ~2000 instructions
 // executed once per wave and launch: instruction fetch is cold, and every taken branch over a cold block breaks the prefetch)
 #define RARE(x) __builtin_expect(!!(x), 0)
-// The optional info planes: in line (round 3).  Until round 2 the benchmark's launches asked for none and the block sat out of
-// line behind RARE(); the headline is now the launch the drop-in really issues (hlx_step with every info plane), and there the
-// block runs in every wave -- out of line it would cost each of them two taken far branches.  -DHLX_INFO_RARE=1: the old layout (A/B).
-#ifndef HLX_INFO_RARE
-#define HLX_INFO_RARE 0
-#endif
-#define INFO_WANTED(x) (HLX_INFO_RARE ? RARE(x) : (x))
 // Pointers that reach the kernel through the hot block (optional outputs) or through *P are GENERIC to the compiler, and a
 // generic access is a FLAT instruction: it counts in vmcnt AND lgkmcnt, may complete out of order with the global ones, and while
 // one may be pending every later `s_waitcnt vmcnt(n)` the compiler emits becomes vmcnt(0) -- on every path, taken or not.  (Found
@@ -95,21 +88,12 @@ template <typename T> DEV gptr_t<T> G(T* p) { return (gptr_t<T>)p; }
 // again before the next launch (whose acquire drops the L2 anyway), and with plain stores the ~21 MB a launch
 // writes would sit dirty in the XCD L2s until the end-of-kernel release writes it all back at once, after the
 // last wave has finished; written through, the bytes leave while the waves still compute and the release finds
-// the L2 clean (MI355X_MICROARCH.md, "stores of each flavour" / publish-large).
-#ifndef HLX_ST_AUX
-#define HLX_ST_AUX 16   // buffer-instruction cache bits: 16 = sc1 (write-through); 0 = plain (A/B builds)
-#endif
+// the L2 clean (MI355X_MICROARCH.md, "stores of each flavour" / publish-large).  The hlx_info_soa.packed words go out the same way.
+constexpr int ST_AUX = 16;   // buffer-instruction cache bits: sc1 (write-through)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 DEV void wt16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, float4 v) {
     u32x4 d = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, HLX_ST_AUX);
-}
-#ifndef HLX_INFO_AUX
-#define HLX_INFO_AUX HLX_ST_AUX   // cache bits of the packed info stores (A/B: 0 = plain)
-#endif
-DEV void wt16i(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, float4 v) {      // hlx_info_soa.packed words
-    u32x4 d = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, HLX_INFO_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, ST_AUX);
 }
 // (pool entries: plain per-lane stores -- a fill touches a few thousand environments)
 struct PoolPtrs {
@@ -130,14 +114,6 @@ DEV PoolPtrs pool_ptrs(float4* arena, int n, int g_planes, int o_planes) {
     p.rf_mask = reinterpret_cast<unsigned long long*>(p.rf_cnt + 4);
     return p;
 }
-// A value whose only reader asks for it in an accumulation register (AGPR) is loaded into one and stays there: the way to keep
-// ~90 prefetched dwords out of the 256 ordinary VGPRs while a section that needs most of those runs (a wave that is alone on its
-// SIMD owns all 512 registers of a lane, but only 256 of them are addressable as ordinary VGPRs).
-DEV float acc_read(float x) {
-    float r;
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(r) : "a"(x));
-    return r;
-}
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 DEV float4 pool_get(const float4* PA, int g) {
     const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)(PA + g * 64);
@@ -150,7 +126,7 @@ DEV void pool_put(float4* PA, int g, double2 v) {
 }
 DEV void wt16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, double2 v) {
     u32x4 d = {(uint32_t)__double2loint(v.x), (uint32_t)__double2hiint(v.x), (uint32_t)__double2loint(v.y), (uint32_t)__double2hiint(v.y)};
-    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, HLX_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, ST_AUX);
 }
 
 // Hot-parameter access: every lane holds two dwords of the 512-byte block (hotw0 = dword `lane`, hotw1 = dword
@@ -228,9 +204,7 @@ template <int BAKE, int OFF> DEV double cold_get(const KParams* P) {
 template <uint32_t SPEC, int MODE /*0 = step, 1 = reset-only, 2 = pool fill*/, bool NOISE, bool PERSIST = false, int LATE = 0, int BAKE = 0>
 // The parity (NOISE) and reset-only (MODE 1) instantiations never run at a size where occupancy matters: they get the
 // whole register file, hence no scratch spills (see tools/check_hot_words.py for why a spilled hot word is fatal).
-#ifndef HLX_WAVES_PER_EU
 #define HLX_WAVES_PER_EU(noise, mode, persist, late) (((noise) || (mode) != 0 || (persist) || (late) == 2) ? 1 : 2)
-#endif
 // waves_per_eu(2): keep the single-step kernels within 256 VGPRs so that two waves fit on a SIMD (they are there anyway: ~205).
 // The fused-rollout instantiations carry the state groups in registers on top of that and do not fit: until round 3 they were
 // held to 256 as well, spilled 30-odd dwords to scratch, and ran 1.5x faster for it once a batch gave a SIMD two waves (1 M
@@ -330,19 +304,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
     const uint32_t lane16 = (uint32_t)lane * 16u;
 #define STG(Gr, v) do { if (MODE == 2) pool_put(PA2, (Gr), (v)); else wt16(rsA, lane16, (uint32_t)(Gr) * 1024u, (v)); } while (0)
     // ... and the dword plane G_AUX (a pool entry holds none: an episode starts with total_fuel_used = 0)
-#ifndef HLX_AB_NO_FU
-#define HLX_AB_NO_FU 0      // timing experiments only: 1 = total_fuel_used neither loaded nor stored
-#endif
-#ifndef HLX_AB_AUX_LATE
-#define HLX_AB_AUX_LATE 0   // A/B: 1 = the total_fuel_used dword is stored in the final burst, not with the early state groups
-#endif
-#ifndef HLX_INFO_W2
-#define HLX_INFO_W2 0       // where hlx_info_soa.packed word 2 leaves: 0 = behind observation pass 0, complete; 1 = with words 0 and 1, and
-#endif                      // its flag dword once more at the end of the kernel, with the detection bits (A/B)
-#ifndef HLX_DONE_LATE
-#define HLX_DONE_LATE 0     // 1 = the done list is compacted behind the observation tile's stores instead of ahead of them (A/B)
-#endif
-#define STAUX(v) do { if (MODE != 2 && !HLX_AB_NO_FU) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsA, (uint32_t)lane * 4u, (uint32_t)G_AUX * 1024u, HLX_ST_AUX); } while (0)
+#define STAUX(v) do { if (MODE != 2) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsA, (uint32_t)lane * 4u, (uint32_t)G_AUX * 1024u, ST_AUX); } while (0)
     // ------------------------------------------------------------------ first load batch, issued at entry
     // (the integrator's state groups and the action row); the Philox draws below do not depend on them and run
     // while the loads are in flight.  The Kalman groups and the ring sample follow as a second batch after Philox.
@@ -354,10 +316,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
     constexpr bool missile_late = MODE == 0 && !((SPEC & KF_DYNAMIC) != 0) && !(SPEC & (HLX_F_OBS_LOS | HLX_F_VOLLEY | HLX_F_ATMOSPHERE));
     // ... and in the small-batch schedule they are LOADED with the second batch, at its head (until round 3 that was the compiler's
     // doing -- it sank the two loads to their first use -- and an unrelated edit undid it; now it is written down)
-#ifndef HLX_MISSILE_LOADS_LATE
-#define HLX_MISSILE_LOADS_LATE 1
-#endif
-    constexpr bool missile_loads_late = HLX_MISSILE_LOADS_LATE && missile_late && LATE != 0 && !PERSIST;
+    constexpr bool missile_loads_late = missile_late && LATE != 0 && !PERSIST;
     float4 g_mpos = make_float4(0.f, 0.f, 0.f, 0.f), g_mvel = g_mpos;
     if (!missile_loads_late) { g_mpos = A[G_MPOS * 64]; g_mvel = A[G_MVEL * 64]; }
     float4 g_thr = make_float4(0.f, 0.f, 0.f, 0.f), g_misc = g_thr;
@@ -368,7 +327,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
     // and advances in every form of the step.  (Round 3 kept it in the CALLER's info plane: a checkpoint lost it.)
     float* const AUX = reinterpret_cast<float*>(arena + (size_t)blockIdx.x * (N_GROUPS * 64) + G_AUX * 64) + lane;
     float g_fu = 0.f;
-    if (MODE == 0 && !HLX_AB_NO_FU) g_fu = *G(AUX);
+    if (MODE == 0) g_fu = *G(AUX);
     // Everything down to the construction of `hot` runs with ALL lanes enabled: the constants are fetched with
     // cross-lane reads (v_readlane), so the lanes that hold them must have executed their loads even in a partial
     // tail block; padding lanes use the last live environment's addresses and their results are discarded.
@@ -433,9 +392,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         // info['fuel_used'] accumulator -- made the machine scheduler hoist the first two Philox rounds, ~60 instructions, above the
         // state loads of the base kernel: the loads left ~350 cycles later and every form of the step lost 0.5 us, old
         // against new library on one box, profiles/r03_ab_loads_before_philox.txt.)
-#ifndef HLX_NO_LOAD_SCHED_BARRIER
         __builtin_amdgcn_sched_barrier(0);
-#endif
         const bool noise_buf = NOISE && P->hot.opt.step_noise != nullptr;    // parity instantiation only
         const bool rnoise_buf = NOISE && P->hot.opt.reset_noise != nullptr;
         const unsigned long long gid = (unsigned long long)(env_offset + i);
@@ -465,13 +422,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 rng.normals4(RS_STEP_N2, n8, n9, n10, n11);
                 float ua = u01(x.x), ub = u01(x.y), uc = u01(x.z), ud = u01(x.w);
                 // keep the block here (the optimiser would otherwise sink each chain to its first use, behind
-                // the loads it is meant to overlap)
-#ifndef HLX_PHILOX_PIN
-#define HLX_PHILOX_PIN 3    // which draws are pinned in front of the first use of loaded state: 3 = all sixteen (rounds 1-3); 2 = not the
-#endif                      // ground-measurement normals of call N2 (first needed in the observation section); 1 = nor the four uniforms (A/B)
+                // the loads it is meant to overlap).  All sixteen draws: leaving the ground-measurement normals of call N2, or the
+                // four uniforms too, to the scheduler costs 0.15 us per Philox call moved out from under the entry loads' shadow
+                // (profiles/r04_ab_philox_pin_negative.txt: contract form 8.80 -> 8.97 -> 9.12 us).
                 asm volatile("" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(n4), "+v"(n5), "+v"(n6), "+v"(n7));
-                if (HLX_PHILOX_PIN >= 3) asm volatile("" : "+v"(n8), "+v"(n9), "+v"(n10), "+v"(n11));
-                if (HLX_PHILOX_PIN >= 2) asm volatile("" : "+v"(ua), "+v"(ub), "+v"(uc), "+v"(ud));
+                asm volatile("" : "+v"(n8), "+v"(n9), "+v"(n10), "+v"(n11));
+                asm volatile("" : "+v"(ua), "+v"(ub), "+v"(uc), "+v"(ud));
                 z_ev = d3((double)n0, (double)n1, (double)n2);
                 z_wind = d3((double)n3, (double)n4, (double)n5);
                 z_gp = d3((double)n6, (double)n7, (double)n8);
@@ -596,11 +552,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             // with actions in [-1, 1] that is never
             if (RARE(fmaxf(fmaxf(fabsf(at.x), fabsf(at.y)), fabsf(at.z)) > 28.f)) {
                 float am = snorm3(at);
-                if (am > 50.f) { at = at * HLX_DIVF(50.f, am); clamped = true; }                  // core.py:1086-1090
+                if (am > 50.f) { at = at * div_rn(50.f, am); clamped = true; }                  // core.py:1086-1090
             }
             if (RARE(fmaxf(fmaxf(fabsf(aw.x), fabsf(aw.y)), fabsf(aw.z)) > 2.8f)) {
                 float gm = snorm3(aw);
-                if (gm > 5.f) { aw = aw * HLX_DIVF(5.f, gm); clamped = true; }                    // core.py:1094-1098
+                if (gm > 5.f) { aw = aw * div_rn(5.f, gm); clamped = true; }                    // core.py:1094-1098
             }
 
             // Is the reference's wind a float64 array at this point?  Simple wind: float32 copy of
@@ -670,9 +626,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 if (angle > 1e-6f) {
                     float half = angle * 0.5f;                                      // angle / 2 (exact)
                     float ch = (float)cos_small((double)half), sh = (float)sin_small((double)half);
-                    Quat r = quat_mul(Quat{ch, HLX_DIVF(ang.x, wn) * sh, HLX_DIVF(ang.y, wn) * sh, HLX_DIVF(ang.z, wn) * sh}, q);
-                    float nq = HLX_SQRTF((float)((((double)(r.w * r.w) + (double)(r.x * r.x)) + (double)(r.y * r.y)) + (double)(r.z * r.z)));
-                    q = Quat{HLX_DIVF(r.w, nq), HLX_DIVF(r.x, nq), HLX_DIVF(r.y, nq), HLX_DIVF(r.z, nq)};
+                    Quat r = quat_mul(Quat{ch, div_rn(ang.x, wn) * sh, div_rn(ang.y, wn) * sh, div_rn(ang.z, wn) * sh}, q);
+                    float nq = sqrt_rn((float)((((double)(r.w * r.w) + (double)(r.x * r.x)) + (double)(r.y * r.y)) + (double)(r.z * r.z)));
+                    q = Quat{div_rn(r.w, nq), div_rn(r.x, nq), div_rn(r.y, nq), div_rn(r.z, nq)};
                 }
             }
             STAMP(4);   // interceptor integrated
@@ -808,7 +764,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             const bool ground = mpos.z <= 0.f;
             const float gdx = mpos.x - HOT(c.target[0]), gdy = mpos.y - HOT(c.target[1]);
             bool near_target = false;                                               // only a missile on the ground asks (rare)
-            if (HAS(HLX_F_VOLLEY) || RARE(ground)) near_target = HLX_SQRTF((float)((double)(gdx * gdx) + (double)(gdy * gdy))) < 500.f;
+            if (HAS(HLX_F_VOLLEY) || RARE(ground)) near_target = sqrt_rn((float)((double)(gdx * gdx) + (double)(gdy * gdy))) < 500.f;
             if (HAS(HLX_F_VOLLEY)) {                                                // :724-748
                 bool all_inactive = true;
 #pragma unroll
@@ -817,7 +773,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         if (vp[k].z <= 0.f) {                                       // on the ground: neutralised
                             vact[k] = false;
                             const float gx = vp[k].x - HOT(c.target[0]), gy = vp[k].y - HOT(c.target[1]);
-                            if (HLX_SQRTF((float)((double)(gx * gx) + (double)(gy * gy))) < 500.f) hit_target = true;
+                            if (sqrt_rn((float)((double)(gx * gx) + (double)(gy * gy))) < 500.f) hit_target = true;
                         }
                         if (vact[k]) all_inactive = false;
                     }
@@ -845,7 +801,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     float md = min_distance;
                     if (crossed) {
                         reward = 3000.f;
-                        if (md < cur_radius) reward = reward + HLX_DIVF(cur_radius - md, cur_radius) * 1000.f;
+                        if (md < cur_radius) reward = reward + div_rn(cur_radius - md, cur_radius) * 1000.f;
                         reward = reward + exp_np(divc(-md, 1.0 / 25.0)) * 500.f;
                         reward = reward + exp_np(divc(-md, 1.0 / 10.0)) * 1000.f;
                         reward = reward + exp_np(divc(-md, 1.0 / 3.0)) * 500.f;
@@ -904,20 +860,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         // One observation pass or two?  (see the observation section below)
         // ... but with the pool at hand (lone-wave schedule) the two-pass flow has no second pass left for a lane whose entry is
         // there -- it observes its terminal state with everybody else and copies the rest -- and is the faster one even when nobody
-        // wants the terminal observation: 7.87 against 8.29 us (profiles/r03_ab_early_state_stores.txt).  -DHLX_LONE_NEVER_SINGLE=0: A/B.
-#ifndef HLX_LONE_NEVER_SINGLE
-#define HLX_LONE_NEVER_SINGLE 1
-#endif
+        // wants the terminal observation: 7.87 against 8.29 us (profiles/r03_ab_early_state_stores.txt, call 5).
         // (A compile-time fact of the lone-wave instantiations -- whether or not the pool is switched on: without the single-pass
         // path in them at all they are 0.15-0.2 us faster in every form, profiles/r03_ab_early_state_stores.txt call 10.)
-        const bool single = (HLX_LONE_NEVER_SINGLE && LONE) ? false : (MODE == 0 && HOT(opt.terminal_obs) == nullptr && !(slots & (1u << 20)));
+        const bool single = LONE ? false : (MODE == 0 && HOT(opt.terminal_obs) == nullptr && !(slots & (1u << 20)));
         // lone-wave schedule: the prepared episode of a lane that has just finished is requested here -- ahead of the output stores
-        // below, so that waiting for it later does not wait for them -- and is unpacked when the observation pass is over
-        // (`pf` is deliberately left without an initial value: it is written and read under `hit_pf` only, and a zero on the
-        // other path makes the compiler merge the two with copies behind the loads -- i.e. wait for them on the spot)
-#ifndef HLX_COOP_RESPAWN
-#define HLX_COOP_RESPAWN 1
-#endif
+        // below, so that waiting for it later does not wait for them -- and stored when the observation pass is over.
         // Round 4: the WAVE copies a prepared episode, not the lane that finished.  The stamps showed where a launch's tail still came
         // from (profiles/r04_stamps_contract_base_p99.txt): the slowest 1-5 % of the waves are the ones with a finished lane, and they
         // spend 3 900 cycles at the loop exit (280 for the others) plus 1 000 in the section that requests the entry -- one lane
@@ -927,20 +875,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         // them per wave; a wave with more computes the others in place), keeps it in ONE register quad through the observation pass,
         // and stores it where that word belongs -- state group l of the finished lane's arena slot, the ring planes, the finished
         // lane's row of the observation tile -- behind the wave's own final stores.  The finished lane's registers keep the old
-        // episode; its own (stale) stores to those addresses are issued first and overwritten in order.  -DHLX_COOP_RESPAWN=0: the
-        // round-3 form (A/B).
+        // episode; its own (stale) stores to those addresses are issued first and overwritten in order.  Against the round-3 form, in
+        // which each finished lane copied its own entry: contract form 8.94 -> 8.83 us, no optional outputs 8.01 -> 7.81, terminal
+        // observations only 8.23 -> 8.02 (profiles/r04_ab_coop_respawn.txt).
         constexpr int COOP_MAX = 4;
-        float4 coop[COOP_MAX];                 // (deliberately uninitialised, like `pf`: written and read under `coop_mask` only)
+        // (`coop` is deliberately left without an initial value: it is written and read under `coop_mask` only, and a zero on the
+        // other path makes the compiler merge the two with copies behind the loads -- i.e. wait for them on the spot)
+        float4 coop[COOP_MAX];
         const bool coop_whole = n - (int)blockIdx.x * 64 >= 64;      // a whole block: every lane of the wave is at work
         unsigned long long coop_mask = 0ull;   // the finished lanes of this wave whose prepared episode the wave copies
         unsigned long long coop_load = 0ull;   // ... as loaded: coop[k] holds the entry of its k-th set bit (the beam check below may clear bits of coop_mask)
         unsigned long long coop_over = 0ull;   // ... and the ones beyond COOP_MAX with a good entry: computed in place, counted apart from misses
         float2 coop_beam = make_float2(2.f, -2.f);   // a finished lane's OWN copy of the beam test its entry was computed with (cosine, threshold)
-        float4 pf[POOL_GROUPS];
-        bool hit_pf = false;
-        if (LONE && HLX_COOP_RESPAWN) {
+        bool coop_hit = false;                 // this lane is one of coop_mask as loaded
+        if (LONE) {
             // (whole blocks only: the copy needs lanes 0 .. POOL_GROUPS - 1 at work; the environments of a partial tail block
             // compute their next episode in place, like any environment whose entry is not there -- same bits)
+            // (The fused rollout computes its respawns in place: its waves drift apart over the steps of a launch, no single step's
+            // stragglers hold it open.  So does the single-pass form: there the copy would wait for memory exactly where the spawn
+            // arithmetic runs today, with nothing saved behind it.)
+            // (... and the schedules for more than one wave per SIMD: there the stragglers of one wave are covered by the other,
+            // and a copy fetched at the end of the pass measured slower than computing -- 16.2 against 15.9 us at 131 072
+            // environments.  The host sets bit 24 for the lone-wave schedule only.)
             if (RARE(__ballot(done) != 0ull) && (slots & (1u << 24)) != 0u && !single && coop_whole) {
                 unsigned long long m = __ballot(done && pre_tag == pre_ep + 1u);
                 const PoolPtrs pq = pool_ptrs(arena, n, g_planes, o_planes);
@@ -956,55 +912,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 }
                 coop_over = m;
                 coop_load = coop_mask;
-                hit_pf = ((coop_mask >> lane) & 1ull) != 0ull;
+                coop_hit = ((coop_mask >> lane) & 1ull) != 0ull;
                 // (the finished lane fetches the two floats that decide whether its entry is still valid for itself: a cross-lane
                 // read of the quad above would be a v_readlane of a register the allocator may have parked in an accumulation
                 // register in between -- the hazard hotcheck.py refuses)
-                if (hit_pf) {
+                if (coop_hit) {
                     typedef float f2v_ __attribute__((ext_vector_type(2)));
                     const f2v_ bt = *(const __attribute__((address_space(1))) f2v_*)(reinterpret_cast<const float*>(PB + (POOL_GROUPS - 1) * 64 + lane) + 2);
                     coop_beam = make_float2(bt.x, bt.y);
                 }
             }
         }
-        if (LONE && !HLX_COOP_RESPAWN) {
-            if (RARE(__ballot(done) != 0ull) && (slots & (1u << 24)) != 0u && !single) {
-                hit_pf = done && pre_tag == pre_ep + 1u;
-                if (hit_pf) {
-                    const PoolPtrs pq = pool_ptrs(arena, n, g_planes, o_planes);
-                    const float4* const PA = pq.pool + (size_t)blockIdx.x * (POOL_GROUPS * 64) + lane;
-#pragma unroll
-                    for (int g = 0; g < POOL_GROUPS; ++g) {
-                        const bool used = g <= G_KFP || (g == G_THRUST && (HAS(HLX_F_THRUST_LAG) || HAS(HLX_F_DOMAIN_RAND))) ||
-                                          (g == G_MISC && HAS(HLX_F_DOMAIN_RAND)) ||
-                                          (g >= G_VPOS && g < N_GROUPS && HAS(HLX_F_VOLLEY) && ((g - G_VPOS) % HLX_MAX_VOLLEY) < VK) ||
-                                          (g == PG_ON && HOT(c.o_delay) > 0) ||
-                                          (g >= PG_GR && g < PG_ROW && HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0) || g >= PG_ROW;
-                        if (used) pf[g] = pool_get(PA, g);
-                    }
-                }
-            }
-        }
-#ifndef HLX_EARLY_STATE_STORES
-#define HLX_EARLY_STATE_STORES 1
-#endif
-#ifndef HLX_EARLY_STATE_POS
-#define HLX_EARLY_STATE_POS 0     // 0: behind the info block (kept); 1: ahead of the scalar outputs (A/B)
-#endif
-        constexpr bool EARLY_ST = HLX_EARLY_STATE_STORES && MODE == 0 && !PERSIST;
-#define HLX_EARLY_BLOCK                                                                    \
-        if (EARLY_ST) {                                                                    \
-            STG(G_IPOS, make_float4(ipos.x, ipos.y, ipos.z, fuel));                        \
-            STG(G_IVEL, make_float4(ivel.x, ivel.y, ivel.z, prev_distance));               \
-            STG(G_QUAT, make_float4(q.w, q.x, q.y, q.z));                                  \
-            STG(G_MPOS, make_float4(mpos.x, mpos.y, mpos.z, min_distance));                \
-            STG(G_MVEL, make_float4(mvel.x, mvel.y, mvel.z, last_distance));               \
-            STG(G_W0, make_double2(wind.x, wind.y));                                       \
-            if (!HLX_AB_AUX_LATE) STAUX(fuel_used);                                        \
-        }
-#if HLX_EARLY_STATE_POS == 1
-        HLX_EARLY_BLOCK
-#endif
+        constexpr bool EARLY_ST = MODE == 0 && !PERSIST;      // the early state stores below
         // ---------------------------------------------------------------------- early scalar outputs
         // The step's scalar outputs go out now, while ~5k cycles of observation math follow.  (Storing the
         // integrator's state groups here as well was measured: +0.5 us/step at 65 536 envs -- the stores
@@ -1015,7 +934,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             reward_out[i] = reward;
             term_out[i] = terminated ? 1 : 0;
             trunc_out[i] = truncated ? 1 : 0;
-            if (INFO_WANTED(slots & (1u << 20))) {   // some hlx_info_soa plane is wanted (one SGPR test instead of nine pointer fetches)
+            // The optional info planes: in line, not behind RARE() (round 3).  Until round 2 the benchmark's launches asked for none and
+            // the block sat out of line; the headline is now the launch the drop-in really issues (hlx_step with every info plane), and
+            // there the block runs in every wave -- out of line it would cost each of them two taken far branches.
+            if (slots & (1u << 20)) {   // some hlx_info_soa plane is wanted (one SGPR test instead of nine pointer fetches)
                 // info['intercepted' | 'missile_hit_target' | 'proximity_fuze_triggered' | 'clamped' | 'crossed_threshold'] (:829-857) and
                 // info['missiles_*'] (:846-847) as they stand at the END OF THE STEP, before an auto-reset clears them (until round 3
                 // `crossed_threshold` of a finished environment was read after its respawn, i.e. always False); the detection bits
@@ -1036,9 +958,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     // eleven 4-byte and four 1-byte stores (1.15 us of the 8.9 us launch for 7.6 % of its bytes).  Words 0 and 1 are
                     // final here; word 2 (missile position + the flag word) leaves behind observation pass 0.
                     rsI = __builtin_amdgcn_make_buffer_rsrc((void*)HOT(opt.info.packed), 0, 0x7FFFFFFF, 0x00020000);
-                    wt16i(rsI, (uint32_t)i * 16u, 0u, make_float4(distance, min_distance, fuel, fuel_used));
-                    wt16i(rsI, (uint32_t)i * 16u, (uint32_t)n * 16u, make_float4(ipos.x, ipos.y, ipos.z, __int_as_float(steps)));   // :836-838
-                    if (HLX_INFO_W2 == 1) wt16i(rsI, (uint32_t)i * 16u, (uint32_t)n * 32u, make_float4(mpos.x, mpos.y, mpos.z, __uint_as_float(info_word)));
+                    wt16(rsI, (uint32_t)i * 16u, 0u, make_float4(distance, min_distance, fuel, fuel_used));
+                    wt16(rsI, (uint32_t)i * 16u, (uint32_t)n * 16u, make_float4(ipos.x, ipos.y, ipos.z, __int_as_float(steps)));   // :836-838
                 }
                 if (RARE(!(slots & (1u << 23)))) {     // separate planes (an `if` of its own behind RARE(), not an `else`: the block then sits out of line)
                     if (HOT(opt.info.distance)) G(HOT(opt.info.distance))[i] = distance;
@@ -1071,12 +992,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         // whose respawn replaces the values, store them again at the end.  Rounds 1 and 2 measured early stores twice and lost
         // 0.5 us both times (plain stores, one load batch); with write-through stores and the second load batch behind Philox
         // the same idea gains 0.5 us in the two-pass forms and is neutral in the single-pass one
-        // (profiles/r03_ab_early_state_stores.txt).  Storing MORE early -- the Kalman groups, the packed word and the ring
-        // samples behind the filter -- loses again (9.96 against 9.74), and so does making this block conditional on the form.
-        // -DHLX_EARLY_STATE_STORES=0: everything in the final burst (A/B).
-#if HLX_EARLY_STATE_POS == 0
-        HLX_EARLY_BLOCK
-#endif
+        // (profiles/r03_ab_early_state_stores.txt, call 1; call 6: 131 072 environments 15.59 -> 14.69 us).  Storing MORE early --
+        // the Kalman groups, the packed word and the ring samples behind the filter -- loses again (9.96 against 9.74), and so
+        // does making this block conditional on the form, storing more of the state inside the observation pass (call 4: the
+        // ground-ring sample behind the ground radar, 9.18 -> 9.63 us; the Kalman groups and the packed word behind the filter,
+        // 9.98), or storing these six groups one block earlier, ahead of the scalar outputs and the info block (call 3: 9.19 -> 9.27).
+        if (EARLY_ST) {
+            STG(G_IPOS, make_float4(ipos.x, ipos.y, ipos.z, fuel));
+            STG(G_IVEL, make_float4(ivel.x, ivel.y, ivel.z, prev_distance));
+            STG(G_QUAT, make_float4(q.w, q.x, q.y, q.z));
+            STG(G_MPOS, make_float4(mpos.x, mpos.y, mpos.z, min_distance));
+            STG(G_MVEL, make_float4(mvel.x, mvel.y, mvel.z, last_distance));
+            STG(G_W0, make_double2(wind.x, wind.y));
+            STAUX(fuel_used);
+        }
         D3 kxp = d3(g_kf0.x, g_kf0.y, g_kf1.x), kxv = d3(g_kf1.y, g_kf2.x, g_kf2.y);
         float p_pp = g_kfp.x, p_pv = g_kfp.y, p_vp = g_kfp.z, p_vv = g_kfp.w;
         // ---------------------------------------------------------------------- observation (+ auto-reset)
@@ -1102,10 +1031,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         // rare, out of line, and the tail of every launch that wants terminal observations) is a SPECIALISED copy: every lane it
         // observes has just respawned -- no delayed samples, no initialised filter, no detection history -- so the Kalman update /
         // predict, the ring reads and their selects are not compiled into it at all, where the shared loop body of rounds 1-2
-        // jumped over them one taken branch at a time.  -DHLX_FRESH_TRIP=0: the second trip as an unspecialised copy (A/B).
-#ifndef HLX_FRESH_TRIP
-#define HLX_FRESH_TRIP 1
-#endif
+        // jumped over them one taken branch at a time.
         float beam_cb = 2.f;      // MODE 2: the beam-test cosine of the entry's first observation (2 = the test was not reached)
         auto trip = [&](auto all_fresh_tag) __attribute__((always_inline)) {
             constexpr bool ALLF = decltype(all_fresh_tag)::value;
@@ -1143,43 +1069,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     epn = (POOL_PRE ? pre_ep : G(pp.ep_cur)[i]) + 1u;
                     if (POOL_PRE || MODE == 2) {
                         const uint32_t tag = POOL_PRE ? pre_tag : G(pp.tag)[i];
-                        // (The fused rollout computes its respawns in place: its waves drift apart over the steps of a launch, no
-                        // single step's stragglers hold it open.  So does the single-pass form: there the copy would wait for memory
-                        // exactly where the spawn arithmetic runs today, with nothing saved behind it.)
-                        // (... and the schedules for more than one wave per SIMD: there the stragglers of one wave are covered by the
-                        // other, and a copy fetched at the end of the pass measured slower than computing -- 16.2 against 15.9 us at
-                        // 131 072 environments.  The host sets bit 24 for the lone-wave schedule only.)
-                        if (POOL_PRE) hit = LONE ? hit_pf : false;
-                        if (LONE && HLX_COOP_RESPAWN) hit = false;      // (decided for the whole wave below: coop_mask)
-                        if (LONE && !HLX_COOP_RESPAWN && hit) {
-                            // The one curriculum scalar the reference really ramps (config.yaml:85-92: the beam width, 120 -> 60 degrees over
-                            // 3 M steps, moved by EVERY call of set_training_step_count) enters a first observation through one decision:
-                            // cosine of the off-boresight angle against the threshold.  The entry carries that cosine and the threshold it
-                            // was compared with; it is the first observation under TODAY's threshold too iff both comparisons fall on
-                            // the same side, by more than the margin inside which the decision replays the reference's arithmetic.
-                            // (A new episode looks straight at its missile -- cosine 1 -- so a ramp through the shipped widths invalidates
-                            // next to nothing, a beam below ~0.5 degrees every in-range entry; rounds
-                            // before this one renewed ALL entries, a 12-45 us launch, ahead of every step of the ramp.)
-                            const float cbe = acc_read(pf[PG_ROW + (HLX_OBS_DIM + 3) / 4 - 1].z), cte = acc_read(pf[PG_ROW + (HLX_OBS_DIM + 3) / 4 - 1].w);
-                            const float ctn = cur_cos_half_beam;
-                            hit = (cbe - ctn > 1e-5f && cbe - cte > 1e-5f) || (ctn - cbe > 1e-5f && cte - cbe > 1e-5f);
-                        }
+                        // (`hit` of a step launch is decided for the whole wave below: coop_mask)
                         (void)tag;
                         if (MODE == 2 && (slots & (1u << 25)) != 0u && tag == epn) done = false;    // renewed since (a fill of every entry)
                     }
                     if (MODE == 2) pool_epn = epn;
                 }
-                if (LONE && HLX_COOP_RESPAWN && coop_mask != 0ull) {
-                    // the beam test each copied entry was computed with, against today's threshold (see the round-3 form below / hlx.h)
+                if (LONE && coop_mask != 0ull) {
+                    // The beam test each copied entry was computed with, against today's threshold (hlx.h).  The one curriculum scalar the
+                    // reference really ramps (config.yaml:85-92: the beam width, 120 -> 60 degrees over 3 M steps, moved by EVERY call of
+                    // set_training_step_count) enters a first observation through one decision: cosine of the off-boresight angle against
+                    // the threshold.  The entry carries that cosine and the threshold it was compared with; it is the first observation
+                    // under TODAY's threshold too iff both comparisons fall on the same side, by more than the margin inside which the
+                    // decision replays the reference's arithmetic.  (A new episode looks straight at its missile -- cosine 1 -- so a ramp
+                    // through the shipped widths invalidates next to nothing, a beam below ~0.5 degrees every in-range entry; round 3
+                    // renewed ALL entries, a 12-45 us launch, ahead of every step of the ramp.)
                     const float ctn = cur_cos_half_beam, cbe = coop_beam.x, cte = coop_beam.y;
                     const bool ok = (cbe - ctn > 1e-5f && cbe - cte > 1e-5f) || (ctn - cbe > 1e-5f && cte - cbe > 1e-5f);
-                    coop_mask &= __ballot(done && hit_pf && ok);
+                    coop_mask &= __ballot(done && coop_hit && ok);
                     hit = done && ((coop_mask >> lane) & 1ull) != 0ull;
                 }
                 if (MODE == 2) dmask = __ballot(done);
                 const unsigned long long smask = __ballot(done && !hit);     // the lanes that compute their respawn here
                 float rd[RS_ITEMS][4];
-                if (!(LONE && HLX_COOP_RESPAWN) || smask != 0ull) {     // (44 moves the wave of a copied episode has no use for)
+                if (!LONE || smask != 0ull) {     // (44 moves the wave of a copied episode has no use for)
 #pragma unroll
                     for (int j = 0; j < RS_ITEMS; ++j) rd[j][0] = rd[j][1] = rd[j][2] = rd[j][3] = 0.f;
                 }
@@ -1244,7 +1157,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         if (smask != 0ull && !single) {    // (the single-pass form computes in place by design: not a miss)
                             // [2] the entry was absent or stale; [3] it was there, but the wave had more finished lanes than it copies for
                             // (a batch-wide truncation step: everyone computing at once is the faster way through that one launch)
-                            const unsigned long long over = LONE && HLX_COOP_RESPAWN ? smask & coop_over : 0ull;
+                            const unsigned long long over = LONE ? smask & coop_over : 0ull;
                             if ((smask & ~over) != 0ull)
                                 (void)__hip_atomic_fetch_add(G(pp.rf_cnt) + 2, __popcll(smask & ~over), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (RARE(over != 0ull))
@@ -1252,7 +1165,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         }
                     }
                 }
-                if (LONE && HLX_COOP_RESPAWN && coop_whole && MODE == 0 && pass == 1 && HOT(opt.terminal_obs)) {
+                if (LONE && coop_whole && MODE == 0 && pass == 1 && HOT(opt.terminal_obs)) {
                     // the terminal observation of every finished lane, copied by the WAVE: lanes 0-12 move one 8-byte pair each of the
                     // finished lane's row of the tile (pass 0's observation of the terminal state) -- one LDS read and one store per
                     // finished lane where the lane itself issued thirteen of each
@@ -1282,7 +1195,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         n_gv = d3((double)rd[5][0], (double)rd[5][1], (double)rd[5][2]);
                     }
                     if (MODE == 0 && pass == 1) {
-                        if (HOT(opt.terminal_obs) && !(LONE && HLX_COOP_RESPAWN && coop_whole)) {
+                        if (HOT(opt.terminal_obs) && !(LONE && coop_whole)) {
                             // the lane's row of the LDS tile (pass 0's observation of the terminal state) -> terminal_obs[i]: all
                             // thirteen 8-byte LDS reads first, then thirteen GLOBAL stores (through a generic pointer the
                             // compiler must assume the store may hit LDS and serialises read / wait / store 26 times)
@@ -1413,73 +1326,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     p_pp = 1000.f; p_pv = 0.f; p_vp = 0.f; p_vv = 1000.f;
                     prev_distance = reld; last_distance = reld; min_distance = reld; // :579-589
                     worsening = 0; crossed = false;
-                    } else if (LONE && HLX_COOP_RESPAWN) {
+                    } else {
                         // the wave copies this lane's prepared episode behind the final stores (below): nothing to unpack.  The dword
                         // plane is the one piece of state an entry does not hold: a new episode has used no fuel
                         fuel_used = 0.f;
-                    } else {
-                        // ---------------- the episode was prepared by a pool fill: state groups, ring samples, observation row
-                        // (unpacked exactly as at kernel entry; what the fill stored is what the store section below packs)
-                        const float4* const PA = pp.pool + (size_t)blockIdx.x * (POOL_GROUPS * 64) + lane;
-                        // (lone-wave schedule: the entry was requested before the observation pass and has been parked in the
-                        // accumulation registers since -- the pass needs the ordinary ones; see acc_read)
-                        const auto PL = [&](int g) {
-                            if (!LONE) return pool_get(PA, g);
-                            return make_float4(acc_read(pf[g].x), acc_read(pf[g].y), acc_read(pf[g].z), acc_read(pf[g].w));
-                        };
-                        const auto dbl = [](float lo, float hi) { return __hiloint2double(__float_as_int(hi), __float_as_int(lo)); };
-                        const float4 a = PL(G_IPOS), b = PL(G_IVEL), c = PL(G_QUAT), d = PL(G_MPOS), e4 = PL(G_MVEL), w0 = PL(G_W0), w1 = PL(G_W1);
-                        const float4 k0 = PL(G_KF0), k1 = PL(G_KF1), k2 = PL(G_KF2), kp = PL(G_KFP);
-                        ipos = v3(a.x, a.y, a.z); fuel = a.w;
-                        ivel = v3(b.x, b.y, b.z); prev_distance = b.w;
-                        q = Quat{c.x, c.y, c.z, c.w};
-                        mpos = v3(d.x, d.y, d.z); min_distance = d.w;
-                        mvel = v3(e4.x, e4.y, e4.z); last_distance = e4.w;
-                        wind = d3(dbl(w0.x, w0.y), dbl(w0.z, w0.w), dbl(w1.x, w1.y));
-                        {
-                            const uint32_t pk = __float_as_uint(w1.z);
-                            steps = (int)(pk & 0x1FFFu); worsening = (int)((pk >> 13) & 0xFFFu);
-                            crossed = (pk >> 25) & 1u; kf_init = (pk >> 26) & 1u; kf_x64 = (pk >> 27) & 1u;
-                            on_delay = (int)(pk >> 28);
-                        }
-                        ep_return = w1.w; fuel_used = 0.f;
-                        kxp = d3(dbl(k0.x, k0.y), dbl(k0.z, k0.w), dbl(k1.x, k1.y));
-                        kxv = d3(dbl(k1.z, k1.w), dbl(k2.x, k2.y), dbl(k2.z, k2.w));
-                        p_pp = kp.x; p_pv = kp.y; p_vp = kp.z; p_vv = kp.w;
-                        if (HAS(HLX_F_THRUST_LAG) || HAS(HLX_F_DOMAIN_RAND)) {
-                            const float4 th = PL(G_THRUST);
-                            thrust_act = v3(th.x, th.y, th.z);
-                            if (HAS(HLX_F_DOMAIN_RAND)) dp.cd_super = th.w;
-                        }
-                        if (HAS(HLX_F_DOMAIN_RAND)) {
-                            const float4 mi = PL(G_MISC);
-                            T0 = dbl(mi.x, mi.y); dp.base_cd = mi.z; dp.peak_m1 = mi.w;
-                        }
-                        if (HAS(HLX_F_VOLLEY)) {
-#pragma unroll
-                            for (int k = 0; k < HLX_MAX_VOLLEY; ++k) {
-                                if (k < VK) {
-                                    const float4 va = PL(G_VPOS + k), vb = PL(G_VVEL + k);
-                                    const uint32_t w = __float_as_uint(vb.w);
-                                    vp[k] = v3(va.x, va.y, va.z); vmin[k] = va.w; vv[k] = v3(vb.x, vb.y, vb.z); vact[k] = (w & 1u) != 0u;
-                                    if (k == 0) { prio = (int)((w >> 8) & 3u); n_int = (int)((w >> 12) & 7u); }
-                                }
-                            }
-                        }
-                        if (HOT(c.o_delay) > 0) on_sample = PL(PG_ON);
-                        if (HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0) {
-                            const float4 s0 = PL(PG_GR), s1 = PL(PG_GR + 1);
-                            g_sp = d3(dbl(s0.x, s0.y), dbl(s0.z, s0.w), dbl(s1.x, s1.y)); g_sq = s1.z; g_sflag = s1.w;
-                            g_s2 = PL(PG_GR + 2);
-                        }
-                        float4 rw[(HLX_OBS_DIM + 3) / 4];
-#pragma unroll
-                        for (int k = 0; k < (HLX_OBS_DIM + 3) / 4; ++k) rw[k] = PL(PG_ROW + k);
-#pragma unroll
-                        for (int k = 0; k < HLX_OBS_DIM; ++k) {
-                            const float4 v = rw[k >> 2];
-                            row[k] = (k & 3) == 0 ? v.x : (k & 3) == 1 ? v.y : (k & 3) == 2 ? v.z : v.w;
-                        }
                     }
                 }
             }
@@ -1489,23 +1339,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 // ======================================================== core.py:511-691 radar detection
                 STAMP2(2);  // close-up: draws selected
                 const V3 rel = mpos - ipos;
-#ifndef HLX_ONBOARD_EARLY
-#define HLX_ONBOARD_EARLY 0
-#endif
                 // The delayed onboard sample (physics v2: core.py:576-593) is a GATHER -- domain randomisation gives every lane its own
                 // delay, i.e. its own ring plane.  It is read in place, where the onboard section needs it (below).  Requesting it
                 // EARLIER has now lost twice: from the physics section behind the second load batch (round 3: +0.8 us), and from here,
                 // the top of the pass, with its registers untouched until the measurement fusion ~2 k cycles further down
-                // (-DHLX_ONBOARD_EARLY=1, round 4: v2dr contract form 11.28 -> 11.65 us, profiles/r04_ab_v2dr_onboard_gather_early.txt).
+                // (round 4: v2dr contract form 11.28 -> 11.65 us, profiles/r04_ab_v2dr_onboard_gather_early.txt).
                 // A 64-line gather at the head of the in-order memory queue holds back the output, info and state stores issued
                 // right behind it; in place it follows them.
-                float4 on_raw = make_float4(0.f, 0.f, 0.f, 0.f);
-                const bool on_have = HOT(c.o_delay) > 0 && !fresh_k && steps >= on_delay;
-                if (HLX_ONBOARD_EARLY && HOT(c.o_delay) > 0 && on_have) {
-                    int slot = o_wslot - on_delay;                            // (t - on_delay) mod o_cap
-                    slot += (slot < 0) ? o_cap : 0;
-                    on_raw = oring[(size_t)slot * N + i];
-                }
                 // ||missile - interceptor|| is at hand: the step's `distance`, or the spawn distance of a lane that has just respawned
                 const float range = (HAS(HLX_F_VOLLEY) || MODE != 0) ? snorm3(rel) : range_c;
                 bool on_det = !(range > HOT(c.radar_range));                             // :539
@@ -1530,7 +1370,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 {                                                                   // :559-566 (straight-line: selects, not a divergent block)
                     float aq = (HOT(c.radar_quality) * (1.0f - (range * HOT(c.inv_radar_range)) * 0.5f)) * cur_on_rel;
                     if (RARE(on_det && fabsf(n_on - aq) < 2e-6f))   // Bernoulli draw within a few ulps of the probability: the reference's own division
-                        aq = (HOT(c.radar_quality) * (1.0f - HLX_DIVF(range, HOT(c.radar_range)) * 0.5f)) * cur_on_rel;
+                        aq = (HOT(c.radar_quality) * (1.0f - div_rn(range, HOT(c.radar_range)) * 0.5f)) * cur_on_rel;
                     const bool miss = on_det && n_on > aq;
                     on_det = on_det && !miss;
                     on_why = miss ? -3.f : on_why;
@@ -1541,7 +1381,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 if (HOT(c.o_delay) > 0) {                                                // :576-588 onboard delay ring
                     on_sample = make_float4(rel.x, rel.y, rel.z, on_det ? 1.f : (HAS(HLX_F_RADAR_DEBUG) ? on_why : 0.f));   // w: 1 detected, -reason otherwise
                     d_on = v3(0.f, 0.f, 0.f); d_on_det = false; on_why = -4.f;              // :582 'sensor_delay_initialization'
-                    if (!HLX_ONBOARD_EARLY && !fresh_k && steps >= on_delay) {
+                    if (!fresh_k && steps >= on_delay) {
                         int slot = o_wslot - on_delay;                            // (t - on_delay) mod o_cap
                         slot += (slot < 0) ? o_cap : 0;
                         float4 s = oring[(size_t)slot * N + i];
@@ -1566,7 +1406,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         const bool chk = g_det && grange > 1e-6f;
                         float se = clampf(g2m.z * __builtin_amdgcn_rcpf(grange), -1.f, 1.f);
                         if (RARE(chk && fminf(fabsf(se - HOT(c.sin_min_elev)), fabsf(se - HOT(c.sin_max_elev))) < 4e-6f))
-                            se = clampf(HLX_DIVF(g2m.z, snorm3(g2m)), -1.f, 1.f);
+                            se = clampf(div_rn(g2m.z, snorm3(g2m)), -1.f, 1.f);
                         g_det = g_det && !(chk && (se < HOT(c.sin_min_elev) || se > HOT(c.sin_max_elev)));
                     }
                     g_det = g_det && !(mpos.z < 50.f);                              // :409
@@ -1577,7 +1417,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     // or the range is small (found with tools/diag_kf.py: the filter state differed by 2e-8 relative from the first
                     // float64 measurement on).  Elsewhere no output shows it above 4e-6 and the step keeps the cheap form.
                     if (HAS(HLX_F_OBS_LOS) || RARE(g_det && fabsf(n_g - dpq) < 2e-6f))
-                        dpq = ((HOT(c.g_base_q) * (1.0f - HLX_DIVF(snorm3(g2m), HOT(c.g_max_range)) * 0.4f)) * HOT(c.weather)) * cur_g_rel;
+                        dpq = ((HOT(c.g_base_q) * (1.0f - div_rn(snorm3(g2m), HOT(c.g_max_range)) * 0.4f)) * HOT(c.weather)) * cur_g_rel;
                     g_det = g_det && !(n_g > dpq);
                     if (g_det) {
                         {
@@ -1610,21 +1450,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     }
                 }
                 const V3 d_gp = to_v3(d_gp64);
-                if (HLX_ONBOARD_EARLY && HOT(c.o_delay) > 0 && on_have) {      // the delayed onboard sample: first touched here
-                    asm volatile("" : "+v"(on_raw.x), "+v"(on_raw.y), "+v"(on_raw.z), "+v"(on_raw.w));
-                    d_on = v3(on_raw.x, on_raw.y, on_raw.z); d_on_det = on_raw.w > 0.f; on_why = d_on_det ? 0.f : on_raw.w;
-                }
-#ifndef HLX_EARLY_MORE
-#define HLX_EARLY_MORE 0      // A/B: 1 = the ground-ring sample is stored behind the ground-radar section; 2 = the Kalman groups and the packed word behind the filter
-#endif
-                if ((HLX_EARLY_MORE & 1) && EARLY_ST && !ALLF && pass == 0 && HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0) {
-                    const uint32_t bb = (uint32_t)min(64, n - (int)blockIdx.x * 64) * 16u;
-                    float4* R = gring + ((size_t)g_wslot * GROUND_RING_WORDS16) * N + (size_t)blockIdx.x * 64;
-                    wt16(__builtin_amdgcn_make_buffer_rsrc(R, 0, bb, 0x00020000), lane16, 0u, make_double2(g_sp.x, g_sp.y));
-                    wt16(__builtin_amdgcn_make_buffer_rsrc(R + N, 0, bb, 0x00020000), lane16, 0u,
-                         make_float4(__int_as_float(__double2loint(g_sp.z)), __int_as_float(__double2hiint(g_sp.z)), g_sq, g_sflag));
-                    wt16(__builtin_amdgcn_make_buffer_rsrc(R + 2 * N, 0, bb, 0x00020000), lane16, 0u, g_s2);
-                }
                 STAMP(9);   // ground radar + ground ring
                 // ---- datalink (core.py:440-474)
                 float datalink = 0.f;
@@ -1691,7 +1516,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         kf_init = true;
                     } else {                                                        // core.py:98-116 on the 2x2 blocks
                         const bool y64 = m64 || kf_x64;
-                        const float sinv = HLX_DIVF(1.0f, p_pp + 400.f);
+                        const float sinv = div_rn(1.0f, p_pp + 400.f);
                         const float kp = p_pp * sinv, kv = p_vp * sinv;
                         if (y64) {
                             const D3 zz = m64 ? zw : to_d3(zf);
@@ -1729,15 +1554,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     }
                     have_track = ALLF ? false : kf_init;
                 }
-                if ((HLX_EARLY_MORE & 2) && EARLY_ST && !ALLF && pass == 0) {
-                    const uint32_t pk = (uint32_t)steps | ((uint32_t)worsening << 13) | ((uint32_t)crossed << 25) |
-                                        ((uint32_t)kf_init << 26) | ((uint32_t)kf_x64 << 27) | ((uint32_t)on_delay << 28);
-                    STG(G_W1, make_float4(__int_as_float(__double2loint(wind.z)), __int_as_float(__double2hiint(wind.z)), __uint_as_float(pk), ep_return));
-                    STG(G_KF0, make_double2(kxp.x, kxp.y));
-                    STG(G_KF1, make_double2(kxp.z, kxv.x));
-                    STG(G_KF2, make_double2(kxv.y, kxv.z));
-                    STG(G_KFP, make_float4(p_pp, p_pv, p_vp, p_vv));
-                }
                 STAMP(11);  // measurement fusion + Kalman filter
                 // ---- observation vector: pure outputs, ordinary fast float32 from here on
                 const float inv_mr = HOT(c.inv_max_range), inv_mv = HOT(c.inv_max_velocity);
@@ -1758,7 +1574,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                         if (kf_x64) {
                             const D3 frp64 = d3(kxp.x - (double)ipos.x, kxp.y - (double)ipos.y, kxp.z - (double)ipos.z);
                             closing = (float)(-ddot(frp64, frv64) / (sqrt(ddot(frp64, frp64)) + 1e-6));
-                        } else closing = -HLX_DIVF(sdot3(frp, frv), snorm3(frp) + 1e-6f);
+                        } else closing = -div_rn(sdot3(frp, frv), snorm3(frp) + 1e-6f);
                     }
                     if (HAS(HLX_F_OBS_LOS)) {                                       // :791-868
                         row[0] = clampf(rrange * inv_mr, 0.f, 1.f);
@@ -1860,22 +1676,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         trip(std::false_type{});
         // hlx_info_soa.packed word 2: the missile as the step left it (a respawn in the second trip replaces it) + the flag word,
         // complete now that pass 0 has decided the detections
-        if (MODE == 0 && HLX_INFO_W2 == 0 && (slots & (1u << 23)) != 0u)
-            wt16i(rsI, (uint32_t)i * 16u, (uint32_t)n * 32u, make_float4(mpos.x, mpos.y, mpos.z, __uint_as_float(info_word | det_bits)));
+        if (MODE == 0 && (slots & (1u << 23)) != 0u)
+            wt16(rsI, (uint32_t)i * 16u, (uint32_t)n * 32u, make_float4(mpos.x, mpos.y, mpos.z, __uint_as_float(info_word | det_bits)));
         // reset()'s info (environment.py:595-601: missile_pos, interceptor_pos, distance, radar_detected, radar_quality) in the words a
         // step writes, for the environments this launch resets -- hlx_reset_info
         if (MODE == 1 && (slots & (1u << 23)) != 0u && done) {
             const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)HOT(opt.info.packed), 0, 0x7FFFFFFF, 0x00020000);
             const uint32_t alive = HAS(HLX_F_VOLLEY) ? (uint32_t)VK : 1u;      // nothing intercepted, every missile of the volley in flight
-            wt16i(rsR, (uint32_t)i * 16u, 0u, make_float4(prev_distance, min_distance, fuel, 0.f));
-            wt16i(rsR, (uint32_t)i * 16u, (uint32_t)n * 16u, make_float4(ipos.x, ipos.y, ipos.z, __int_as_float(0)));
-            wt16i(rsR, (uint32_t)i * 16u, (uint32_t)n * 32u, make_float4(mpos.x, mpos.y, mpos.z, __uint_as_float(det_bits | (alive << 12))));
+            wt16(rsR, (uint32_t)i * 16u, 0u, make_float4(prev_distance, min_distance, fuel, 0.f));
+            wt16(rsR, (uint32_t)i * 16u, (uint32_t)n * 16u, make_float4(ipos.x, ipos.y, ipos.z, __int_as_float(0)));
+            wt16(rsR, (uint32_t)i * 16u, (uint32_t)n * 32u, make_float4(mpos.x, mpos.y, mpos.z, __uint_as_float(det_bits | (alive << 12))));
         }
-#if HLX_FRESH_TRIP
         if (RARE(again)) trip(std::true_type{});
-#else
-        if (RARE(again)) trip(std::false_type{});
-#endif
 
         STAMP(13);  // observation passes (incl. loop exit)
         // ---------------------------------------------------------------------- store state + rings
@@ -1885,25 +1697,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             // fused rollout: the state stays in the registers it was loaded into; otherwise it goes back to the arena
 #define PUT4(G, reg, ...) do { if (PERSIST) reg = __VA_ARGS__; else STG(G, __VA_ARGS__); } while (0)
 #define PUT2(G, reg, ...) do { if (PERSIST) reg = __VA_ARGS__; else STG(G, __VA_ARGS__); } while (0)
-            if (!EARLY_ST || RARE(done && !(LONE && HLX_COOP_RESPAWN && ((coop_mask >> lane) & 1ull) != 0ull))) {
+            if (!EARLY_ST || RARE(done && !(LONE && ((coop_mask >> lane) & 1ull) != 0ull))) {
             PUT4(G_IPOS, g_ipos, make_float4(ipos.x, ipos.y, ipos.z, fuel));
             PUT4(G_IVEL, g_ivel, make_float4(ivel.x, ivel.y, ivel.z, prev_distance));
             PUT4(G_QUAT, g_quat, make_float4(q.w, q.x, q.y, q.z));
             PUT4(G_MPOS, g_mpos, make_float4(mpos.x, mpos.y, mpos.z, min_distance));
             PUT4(G_MVEL, g_mvel, make_float4(mvel.x, mvel.y, mvel.z, last_distance));
             PUT2(G_W0, g_w0, make_double2(wind.x, wind.y));
-            if (PERSIST) g_fu = fuel_used; else if (!HLX_AB_AUX_LATE) STAUX(fuel_used);
+            if (PERSIST) g_fu = fuel_used; else STAUX(fuel_used);
             }
-            if (HLX_AB_AUX_LATE && !PERSIST) STAUX(fuel_used);
             if (HAS(HLX_F_THRUST_LAG) || HAS(HLX_F_DOMAIN_RAND)) PUT4(G_THRUST, g_thr, make_float4(thrust_act.x, thrust_act.y, thrust_act.z, dp.cd_super));
-            if (!((HLX_EARLY_MORE & 2) && EARLY_ST) || RARE(done)) {
             PUT4(G_W1, g_w1, make_float4(__int_as_float(__double2loint(wind.z)), __int_as_float(__double2hiint(wind.z)),
                                          __uint_as_float(packed), ep_return));
             PUT2(G_KF0, g_kf0, make_double2(kxp.x, kxp.y));
             PUT2(G_KF1, g_kf1, make_double2(kxp.z, kxv.x));
             PUT2(G_KF2, g_kf2, make_double2(kxv.y, kxv.z));
             PUT4(G_KFP, g_kfp, make_float4(p_pp, p_pv, p_vp, p_vv));
-            }
             if (HAS(HLX_F_DOMAIN_RAND)) PUT4(G_MISC, g_misc, make_float4(__int_as_float(__double2loint(T0)), __int_as_float(__double2hiint(T0)), dp.base_cd, dp.peak_m1));
             if (HAS(HLX_F_VOLLEY)) {
 #pragma unroll
@@ -1936,7 +1745,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                     oring + (size_t)o_wslot * N + (size_t)blockIdx.x * 64, 0, blk_bytes, 0x00020000);
                 wt16(rsO, lane16, 0u, on_sample);
             }
-            if (MODE != 2 && HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0 && (!((HLX_EARLY_MORE & 1) && EARLY_ST) || RARE(done))) {
+            if (MODE != 2 && HAS(HLX_F_GROUND) && HOT(c.g_delay) > 0) {
                 // the slot's three planes are N words apart: one descriptor per plane keeps every offset 32-bit at any N
                 float4* R = gring + ((size_t)g_wslot * GROUND_RING_WORDS16) * N + (size_t)blockIdx.x * 64;
                 wt16(__builtin_amdgcn_make_buffer_rsrc(R, 0, blk_bytes, 0x00020000), lane16, 0u, make_double2(g_sp.x, g_sp.y));
@@ -1945,7 +1754,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
                 wt16(__builtin_amdgcn_make_buffer_rsrc(R + 2 * N, 0, blk_bytes, 0x00020000), lane16, 0u, g_s2);
             }
         }
-        if (LONE && HLX_COOP_RESPAWN && RARE(coop_mask != 0ull)) {
+        if (LONE && RARE(coop_mask != 0ull)) {
             // ---- the wave stores the prepared episodes it holds: word `lane` of each entry goes where the finished lane's own final
             // stores (just issued, with the OLD episode's values) put that word.  One descriptor over the whole allocation: arena
             // blocks, ground ring and onboard ring all lie behind `arena` (hlx_host.inc), offsets fit 32 bits at the batch sizes the
@@ -1988,26 +1797,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
         if (MODE == 0) {
             if (RARE((slots & (1u << 20)) && !(slots & (1u << 23))) && HOT(opt.info.flags))
                 G(HOT(opt.info.flags))[i] = (uint8_t)(info_word | det_bits);
-            if (HLX_INFO_W2 == 1 && (slots & (1u << 23)) != 0u)      // the flag dword of word 2 once more, detection bits included
-                __builtin_amdgcn_raw_buffer_store_b32(info_word | det_bits, rsI, (uint32_t)i * 16u + 12u, (uint32_t)n * 32u, HLX_INFO_AUX);
         }
         }   // if (live)
     }
 
     STAMP(14);      // state / ring / scalar outputs stored
-#define HLX_COMPACTION_BLOCK \
-        if (MODE == 0 && !PERSIST && done_idx_out) { \
-            const unsigned long long m = __ballot(live && done); \
-            if (m) { \
-                int base = 0; \
-                if (lane == 0) base = __hip_atomic_fetch_add(G(P->done_cnt) + (int)(t & 1ull), __popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
-                base = __shfl(base, 0); \
-                if (live && done) G(done_idx_out)[base + __popcll(m & ((1ull << lane) - 1ull))] = i; \
-            } \
-        } \
-
     // -------------------------------------------------------------------------- done-mask compaction
-    if (!HLX_DONE_LATE) { HLX_COMPACTION_BLOCK }
+    if (MODE == 0 && !PERSIST && done_idx_out) {
+        const unsigned long long m = __ballot(live && done);
+        if (m) {
+            int base = 0;
+            if (lane == 0) base = __hip_atomic_fetch_add(G(P->done_cnt) + (int)(t & 1ull), __popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            base = __shfl(base, 0);
+            if (live && done) G(done_idx_out)[base + __popcll(m & ((1ull << lane) - 1ull))] = i;
+        }
+    }
     // Every step launch arms the counter of the NEXT vec step, whether or not this one compacts: listed and unlisted
     // steps (hlx_step without done_idx, hlx_rollout, the fused rollout) may interleave freely.
     if (MODE == 0 && !PERSIST && blockIdx.x == 0 && lane == 0) G(P->done_cnt)[(int)((t + 1ull) & 1ull)] = 0;
@@ -2077,7 +1881,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
             for (int k = 0; k < HLX_OBS_DIM; ++k) dst[lane * HLX_OBS_DIM + k] = row[k];
         }
     }
-    if (HLX_DONE_LATE) { HLX_COMPACTION_BLOCK }
     STAMP(15);      // observation tile stored
     if (PERSIST) {   // next step of the fused rollout: clock, ring slots (mod their capacities), I/O cursors
         t += 1ull;

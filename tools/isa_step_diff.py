@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Compare the instruction streams of every step-kernel instantiation (hlx_env_kernel<...>) of two builds of libhlx.so,
-without a GPU: `python tools/isa_step_diff.py OLD.so NEW.so`.  Addresses and the scratch file names of the code objects
-are ignored; exit status 1 if an instantiation is missing or differs.  For changes that must leave the step kernel alone
-(new kernels beside it, host code)."""
+without a GPU: `python tools/isa_step_diff.py [--all] OLD.so NEW.so`.  `--all`: every kernel of the code objects (observation,
+evaluation, HRL and self-test kernels as well).  Addresses and the scratch file names of the code objects are ignored; exit
+status 1 if a kernel is missing or differs.  For changes that must leave the step kernel (or, with --all, every kernel) alone."""
 import os
 import re
 import sys
@@ -11,12 +11,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hlynr_intercept_amd import hotcheck  # noqa: E402
 
 
-def step_kernels(path):
+def kernels(path, every=False):
     out, cur = {}, None
     for line in hotcheck.listing(path).splitlines():
         m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
         if m:
-            cur = m.group(1) if "hlx_env_kernel" in m.group(1) else None
+            cur = m.group(1) if every or "hlx_env_kernel" in m.group(1) else None
             if cur:
                 out[cur] = []
         elif cur and "file format" not in line:
@@ -24,14 +24,17 @@ def step_kernels(path):
     return out
 
 
-def main(old, new):
-    a, b = step_kernels(old), step_kernels(new)
+def main(argv):
+    every = "--all" in argv
+    old, new = [a for a in argv if a != "--all"][:2]
+    a, b = kernels(old, every), kernels(new, every)
     bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
     for k in bad:
         print("DIFFERS" if k in a and k in b else "ONLY IN " + ("OLD" if k in a else "NEW"), k)
-    print(f"{len(set(a) & set(b)) - len([k for k in bad if k in a and k in b])} of {len(set(a) | set(b))} step-kernel instantiations identical")
+    what = "kernels" if every else "step-kernel instantiations"
+    print(f"{len(set(a) & set(b)) - len([k for k in bad if k in a and k in b])} of {len(set(a) | set(b))} {what} identical")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    sys.exit(main(sys.argv[1:]))
