@@ -1,6 +1,7 @@
 """Builds the HIP shared library in-tree: hlynr_intercept_amd/libhlx.so (gfx950 only)."""
 from __future__ import annotations
 
+import fcntl
 import os
 import shutil
 import subprocess
@@ -8,12 +9,19 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.environ.get("HLX_LIBRARY") or os.path.join(_HERE, "libhlx.so")   # HLX_LIBRARY: diagnostic builds
-SOURCES = ["hlx_kernels.hip"]
-DEPS = ["hlx_kernels.hip", "hlx_inst_gen.h", "hlx_host.inc", "hlx_obs.inc", "hlx_device.h", "hlx_kargs.h", "hlx_kcfg.h", "hlx_bake_gen.cpp", os.path.join("..", "..", "include", "hlx.h"),
+SAFE_LIB = os.path.join(_HERE, "libhlx_safe.so")
+LOCK = os.path.join(_HERE, "libhlx.so.lock")     # held by every step of a build that writes: headers, libraries, sidecars
+SOURCE = os.path.join(CSRC, "hlx_kernels.hip")
+# not hlx_inst_gen.h: it decides in which translation unit an instantiation is compiled, not what the library contains
+DEPS = ["hlx_kernels.hip", "hlx_host.inc", "hlx_obs.inc", "hlx_device.h", "hlx_kargs.h", "hlx_kcfg.h", "hlx_bake_gen.cpp", os.path.join("..", "..", "include", "hlx.h"),
         os.path.join("..", "..", "include", "hlx_obs.h"), "hlx_hrl.inc", os.path.join("..", "..", "include", "hlx_hrl.h"),
         "hlx_eval.inc", os.path.join("..", "..", "include", "hlx_eval.h")]
 
-
+# Every compilation of hlx_kernels.hip -- product, safe, diagnostic and A/B builds -- starts from these flags and adds only defines
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=16",
+         "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-Wno-unused-value"]
+# -z defs: a launcher declared `extern template` in the host unit and defined in no part fails the link, not the dlopen
+LINK = ["-shared", "-Wl,-z,defs"]
 SAFE_FLAGS = ["-DHLX_HOT_FROM_MEMORY=1"]
 
 
@@ -142,135 +150,45 @@ def _listed() -> int:
         return 0
 
 
-def _compile_parallel(flags, extra, out, verbose):
-    """The library from PARTS + 1 translation units compiled at once (hlx_kernels.hip, "Launchers"), linked into `out`."""
+def _jobs() -> int:
+    """Compilers at once: MAX_JOBS when set, never more than 16, nor more than this machine has CPUs."""
+    return max(1, min(16, int(os.environ.get("MAX_JOBS") or 16), os.cpu_count() or 1))
+
+
+def _compile(targets, verbose: bool = False) -> None:
+    """hlx_kernels.hip once per (output, defines, split) target, all units in one pool.  split: PARTS + 1 units (hlx_kernels.hip,
+    "Launchers") when csrc/hlx_inst_gen.h lists instantiations and HLX_SINGLE_TU is unset; a failure there: one unit."""
     import tempfile
-    from concurrent.futures import ThreadPoolExecutor
-    src = os.path.join(CSRC, SOURCES[0])
-    cflags = [f for f in flags if f != "-shared"]
-    with tempfile.TemporaryDirectory(dir=_HERE) as tmp:
-        jobs = [(os.path.join(tmp, "host.o"), ["-DHLX_TU_HOST"])] + [(os.path.join(tmp, f"part{k}.o"), [f"-DHLX_TU_PART={k}"]) for k in range(PARTS)]
+    from concurrent.futures import ThreadPoolExecutor, wait
 
-        def one(job):
-            obj, defs = job
-            cmd = [_hipcc()] + cflags + extra + defs + ["-c", "-o", obj, src]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd, cwd=CSRC)
-            return obj
-
-        with ThreadPoolExecutor(max_workers=min(len(jobs), max(1, (os.cpu_count() or 2)))) as pool:
-            objs = list(pool.map(one, jobs))
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+    def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd, cwd=CSRC)
 
+    def single(out, defines):
+        return [_hipcc()] + FLAGS + defines + LINK + ["-o", out, SOURCE]
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """Build (if needed) under an exclusive file lock: processes started together (pytest-xdist, several ranks without
-    LOCAL_RANK, notebooks) queue up instead of compiling into the same file; the compiler writes to a name unique to this
-    process and the result is renamed into place only after the hot-word check has passed."""
-    import fcntl
-    if not force and not needs_build():
-        return LIB
-    with open(LIB + ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and not needs_build():      # somebody else built it while this process waited
-                return LIB
-            generate_baked(verbose)
-            tmp = f"{LIB}.{os.getpid()}.unverified"
-            flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=16",
-                     "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-Wno-unused-value"]
-
-            def compile_(extra):
-                # several translation units at once when csrc/hlx_inst_gen.h says how to split the instantiations (HLX_SINGLE_TU=1:
-                # never); any failure on that path falls back to the single translation unit of rounds 1-4
-                if _listed() and not os.environ.get("HLX_SINGLE_TU"):
-                    try:
-                        _compile_parallel(flags, extra, tmp, verbose)
-                        return
-                    except Exception as why:
-                        print(f"hlynr_intercept_amd.build: parallel build failed ({why}); compiling one translation unit", flush=True)
-                cmd = [_hipcc()] + flags + extra + ["-o", tmp] + [os.path.join(CSRC, s) for s in SOURCES]
-                if verbose:
-                    print(" ".join(cmd))
-                subprocess.check_call(cmd, cwd=CSRC)
-
-            safe = bool(os.environ.get("HLX_SAFE_BUILD"))       # force the safe build (tests; a toolchain known to need it)
-            compile_(SAFE_FLAGS if safe else [])
-            # the constants of the step kernel are fetched across lanes (v_readlane): a register-allocator spill of those two
-            # VGPRs would silently corrupt them, so the code object is inspected before the library is put in place
-            from . import hotcheck
-            if not safe:
-                try:
-                    hotcheck.verify(tmp)
-                except hotcheck.HotcheckToolsMissing:
-                    os.replace(tmp, LIB + ".unchecked")
+    split_ok = _listed() and not os.environ.get("HLX_SINGLE_TU")
+    with tempfile.TemporaryDirectory(dir=_HERE) as tmp, ThreadPoolExecutor(_jobs()) as pool:
+        work = []
+        for i, (out, defines, split) in enumerate(targets):
+            units = [["-DHLX_TU_HOST"]] + [[f"-DHLX_TU_PART={k}"] for k in range(PARTS)] if split and split_ok else []
+            objs = [os.path.join(tmp, f"{i}.{k}.o") for k in range(len(units))]
+            cmds = [[_hipcc()] + FLAGS + defines + u + ["-c", "-o", o, SOURCE] for u, o in zip(units, objs)] or [single(out, defines)]
+            work.append((out, defines, objs, [pool.submit(run, c) for c in cmds]))
+        for out, defines, objs, futures in work:
+            wait(futures)           # every unit has ended before the fallback starts
+            try:
+                for f in futures:
+                    f.result()
+                if objs:
+                    pool.submit(run, [_hipcc(), "--offload-arch=gfx950", "-fPIC"] + LINK + ["-o", out] + objs).result()
+            except Exception as why:
+                if not objs:
                     raise
-                except hotcheck.HotcheckViolation as why:
-                    # This compiler does to a hot-word register what the cross-lane scheme cannot survive.  Not a reason to have no
-                    # library: the SAFE build reads the same constants from memory -- same results, slower (hlx_kernels.hip,
-                    # HLX_HOT_FROM_MEMORY) -- and says so (hlx_hot_words_from_memory(), bench.py's line, the marker file).
-                    os.replace(tmp, LIB + ".rejected")
-                    print(f"hlynr_intercept_amd.build: {why}\n  -> building the SAFE variant (-DHLX_HOT_FROM_MEMORY=1) instead", flush=True)
-                    safe = True
-                    compile_(SAFE_FLAGS)
-                except Exception:
-                    os.replace(tmp, LIB + ".rejected")
-                    raise
-            marker = LIB + ".safe"
-            if safe:
-                with open(marker, "w") as f:
-                    f.write("built with -DHLX_HOT_FROM_MEMORY=1 (hot constants read from memory; see build.py)\n")
-            elif os.path.exists(marker):
-                os.remove(marker)
-            os.replace(tmp, LIB)
-            try:      # where the NEXT build compiles what: from what this one contains (a hint file: never a reason to fail)
-                write_inst_list(instantiations(hotcheck.listing(LIB)), verbose)
-            except Exception:
-                pass
-            with open(LIB + ".srchash", "w") as f:
-                f.write(_src_hash() + "\n")
-            return LIB
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-
-
-SAFE_LIB = os.path.join(_HERE, "libhlx_safe.so")
-
-
-def build_safe(force: bool = False, minimal: bool = False) -> str:
-    """The SAFE variant beside the product library (hlynr_intercept_amd/libhlx_safe.so, never loaded by default): what
-    tests/test_safe_build_gpu.py compares with the product build bit for bit.  `minimal`: the base kernel variant only (seconds
-    instead of minutes).  Returns the path; up to date when its sidecar holds the current source hash (+ the variant)."""
-    want = _src_hash() + (" minimal" if minimal else " full")
-    try:
-        with open(SAFE_LIB + ".srchash") as f:
-            have = f.read().strip()
-    except OSError:
-        have = ""
-    if not force and os.path.exists(SAFE_LIB) and (have == want or (minimal and have == _src_hash() + " full")):
-        return SAFE_LIB
-    generate_baked(False)
-    tmp = f"{SAFE_LIB}.{os.getpid()}.tmp"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=16",
-             "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-Wno-unused-value"]
-    done = False
-    if not minimal and _listed() and not os.environ.get("HLX_SINGLE_TU"):
-        try:
-            _compile_parallel(flags, SAFE_FLAGS, tmp, False)
-            done = True
-        except Exception as why:
-            print(f"hlynr_intercept_amd.build: parallel build of the safe variant failed ({why}); compiling one translation unit", flush=True)
-    if not done:
-        subprocess.check_call([_hipcc()] + flags + SAFE_FLAGS + (["-DHLX_AB_MINIMAL"] if minimal else []) + ["-o", tmp] +
-                              [os.path.join(CSRC, s) for s in SOURCES], cwd=CSRC)
-    os.replace(tmp, SAFE_LIB)
-    with open(SAFE_LIB + ".srchash", "w") as f:
-        f.write(want + "\n")
-    return SAFE_LIB
+                print(f"hlynr_intercept_amd.build: parallel build of {out} failed ({why}); compiling one translation unit", flush=True)
+                pool.submit(run, single(out, defines)).result()
 
 
 def safe_lib_variants() -> str:
@@ -283,13 +201,94 @@ def safe_lib_variants() -> str:
         return ""
 
 
+def _build(force: bool, verbose: bool, product: bool, safe: str) -> None:
+    """libhlx.so if `product`, libhlx_safe.so if `safe` ('full', or 'minimal': the base kernel variant only), each if forced or out
+    of date.  The product is renamed into place only after the hot-word check; both sidecars record the hash of what was compiled."""
+    def todo():
+        return product and (force or needs_build()), bool(safe) and (force or safe_lib_variants() not in ("full", safe))
+
+    if not any(todo()):
+        return
+    with open(LOCK, "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        do_lib, do_safe = todo()        # somebody else may have built it while this process waited
+        if not (do_lib or do_safe):
+            return
+        generate_baked(verbose)
+        src_hash = _src_hash()
+        tmp, safe_tmp = f"{LIB}.{os.getpid()}.unverified", f"{SAFE_LIB}.{os.getpid()}.unverified"
+        safe_only = bool(os.environ.get("HLX_SAFE_BUILD"))       # force the safe build (tests; a toolchain known to need it)
+        targets = [(tmp, SAFE_FLAGS if safe_only else [], True)] if do_lib else []
+        if do_safe:
+            targets.append((safe_tmp, SAFE_FLAGS + (["-DHLX_AB_MINIMAL"] if safe == "minimal" else []), safe == "full"))
+        _compile(targets, verbose)
+        from . import hotcheck
+        if do_lib and not safe_only:
+            # the constants of the step kernel are fetched across lanes (v_readlane): a register-allocator spill of those two
+            # VGPRs would silently corrupt them, so the code object is inspected before the library is put in place
+            try:
+                hotcheck.verify(tmp)
+            except hotcheck.HotcheckToolsMissing:
+                os.replace(tmp, LIB + ".unchecked")
+                raise
+            except hotcheck.HotcheckViolation as why:
+                # This compiler does to a hot-word register what the cross-lane scheme cannot survive.  Not a reason to have no
+                # library: the SAFE build reads the same constants from memory -- same results, slower (hlx_kernels.hip,
+                # HLX_HOT_FROM_MEMORY) -- and says so (hlx_hot_words_from_memory(), bench.py's line, the marker file).
+                os.replace(tmp, LIB + ".rejected")
+                print(f"hlynr_intercept_amd.build: {why}\n  -> building the SAFE variant (-DHLX_HOT_FROM_MEMORY=1) instead", flush=True)
+                safe_only = True
+                _compile([(tmp, SAFE_FLAGS, True)], verbose)
+            except Exception:
+                os.replace(tmp, LIB + ".rejected")
+                raise
+        if do_lib:
+            marker = LIB + ".safe"
+            if safe_only:
+                with open(marker, "w") as f:
+                    f.write("built with -DHLX_HOT_FROM_MEMORY=1 (hot constants read from memory; see build.py)\n")
+            elif os.path.exists(marker):
+                os.remove(marker)
+            os.replace(tmp, LIB)
+        if do_safe:
+            os.replace(safe_tmp, SAFE_LIB)
+        for done, path, text in ((do_lib, LIB, src_hash), (do_safe, SAFE_LIB, f"{src_hash} {safe}")):
+            if done:
+                with open(path + ".srchash", "w") as f:
+                    f.write(text + "\n")
+        if do_lib:
+            try:      # where the NEXT build compiles what: from what this one contains (a hint file: never a reason to fail)
+                write_inst_list(instantiations(hotcheck.listing(LIB)), verbose)
+            except Exception:
+                pass
+
+
+def build(force: bool = False, verbose: bool = False, with_safe: bool = False) -> str:
+    """libhlx.so, built if forced or out of date (content hash in libhlx.so.srchash); `with_safe`: the full safe library too, its
+    translation units in the same pool of compilers.  Returns the path of the product library."""
+    _build(force, verbose, True, "full" if with_safe else "")
+    return LIB
+
+
+def build_safe(force: bool = False, minimal: bool = False) -> str:
+    """The SAFE variant beside the product library (hlynr_intercept_amd/libhlx_safe.so, never loaded by default): what
+    tests/test_safe_build_gpu.py compares with the product build bit for bit.  `minimal`: the base kernel variant only (seconds
+    instead of minutes).  Returns the path; up to date when its sidecar holds the current source hash (+ the variant)."""
+    _build(force, False, False, "minimal" if minimal else "full")
+    return SAFE_LIB
+
+
+def build_variant(out: str, defines) -> str:
+    """hlx_kernels.hip with extra `defines` as one translation unit into `out`, under the build lock (A/B and diagnostic builds)."""
+    with open(LOCK, "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        _compile([(out, list(defines), False)])
+    return out
+
+
 def build_stamps(level: int = 1) -> str:
     """Diagnostic build with s_memtime stamps (tools/diag_stamps.py); never used by the product path."""
-    out = os.path.join(_HERE, "libhlx_stamps.so")
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-mllvm", "-amdgpu-kernarg-preload-count=16", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-Wno-unused-value", f"-DHLX_STAMPS={level}", "-o", out] + [os.path.join(CSRC, s) for s in SOURCES],
-                          cwd=CSRC)
-    return out
+    return build_variant(os.path.join(_HERE, "libhlx_stamps.so"), [f"-DHLX_STAMPS={level}"])
 
 
 if __name__ == "__main__":

@@ -1913,8 +1913,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HLX_WAVES_PE
 //   -DHLX_TU_PART=k : the kernel code and the explicit instantiations of the launchers csrc/hlx_inst_gen.h lists for part k, nothing else;
 //   -DHLX_TU_HOST   : everything else (the C ABI, the observation pipeline, the HRL controller), with those launchers declared
 //                     `extern template` -- a launcher the list does not name is instantiated here as always, so the list is a hint about
-//                     where to compile, never about what exists (build.py regenerates it from every library it has built).
-// Neither macro: the single translation unit of rounds 1-4 (A/B builds, fallback).  The kernels stay in the unnamed namespace: their
+//                     where to compile, never about what exists (build.py regenerates it from every library it has built, after
+//                     the last unit of that build has compiled, so all units of one build read the same list; the link uses
+//                     -z defs, so a launcher declared here and defined in no part fails it and the single unit is built instead).
+// Neither macro: the single translation unit of rounds 1-4 (A/B, diagnostic and minimal builds, fallback).  The kernels stay in the unnamed namespace: their
 // names, and everything hotcheck.py and the tools read off the code objects, are the same in all three forms.
 namespace hlx_launchers {
 struct StepArgs {
